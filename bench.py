@@ -20,6 +20,12 @@ model (4 B * N_in + 16 B * W*H) is reported beside it as `model_*` -- with ESS +
 skips most of those samples, so that model exceeds the HBM peak and is never the fraction.
 cpu_baseline = the reference's CPU ray-cast path (myApp.cu:1401-1495, restated in oracle/) on a
 bounded column subset of the same frame, one host thread (the reference's own threading).
+
+A plain run does what the headline needs and no more: set up, warm up, time --steps frames, write
+--dump-outputs, print the line.  --full adds what takes runs of its own: cpu_baseline, extra.*
+(single-frame, exact, oblique and moving-camera rates, the C4 / C5 configs and their bitwise check),
+the untimed per-launch pass (kernel_ms_mean, *_per_launch) and the counting frames (samples_*,
+n_in_dataset_samples, *_marched, model_*); a plain line carries null there.
 """
 import argparse
 import json
@@ -85,7 +91,42 @@ def parse():
                          "(1: C4; 2: C4 and C5)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="PMC traffic summary (tools/pmc_traffic.py) to attach when it matches this workload")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the CPU baseline (--cpu-baseline), the "
+                         "exact / oblique / moving-camera / single-frame rates (--extra), the C4 / C5 configs "
+                         "(--extra-configs, --check-extras), the untimed per-launch pass (roofline.kernel_ms_mean) "
+                         "and the counting frames (samples_marched, n_in_dataset_samples, frac_marched, model_*). "
+                         "A plain run sets up, warms up, times --steps frames and prints the line; those fields "
+                         "are null in it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step rendered to DIR/frame.npy "
+                         "(float32 (W, H, 4); a frame above DUMP_MAX_BYTES is written as a fixed seeded sample of "
+                         "its pixels, with their flat indices in DIR/frame_pixels.npy)")
+    a = ap.parse_args()
+    if not a.full:
+        a.cpu_baseline, a.extra, a.extra_configs = 0, 0, ""
+    return a
+
+
+DUMP_MAX_BYTES = 48 << 20   # of --dump-outputs, all files together (the frame, or sample + indices)
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(dirname, frame):
+    """--dump-outputs: the (W, H, 4) float32 device frame of the last timed step as DIR/frame.npy.  A
+    frame above DUMP_MAX_BYTES (C5: 133 MB) is written as a sample of its pixels -- the same sorted
+    pixel set every run (DUMP_SEED) -- as (n, 4) float32, with the pixels' flat indices x * H + y in
+    DIR/frame_pixels.npy (float64: exact below 2^53)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = frame.detach().cpu().numpy().astype(np.float32, copy=False)
+    if host.nbytes > DUMP_MAX_BYTES:
+        npix = host.shape[0] * host.shape[1]
+        n = DUMP_MAX_BYTES // (16 + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(npix, size=n, replace=False))
+        np.save(os.path.join(dirname, "frame_pixels.npy"), idx.astype(np.float64))
+        host = host.reshape(npix, 4)[idx]
+    np.save(os.path.join(dirname, "frame.npy"), np.ascontiguousarray(host))
 
 
 def fail(msg):
@@ -362,6 +403,17 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     frame_ms_device = ev0.elapsed_time(ev1) / a.steps
+    if a.dump_outputs and rank == 0:
+        # the frame the last timed step rendered: the ring slot before the submitter's next one, or
+        # the Python farm's last assembled frame
+        if sub is not None:
+            last = frames_dev[(sub.pos - 1) % B] if a.steps else None
+        else:
+            last = farm._ordered_frame() if a.steps else None
+        if last is None:
+            fail("--dump-outputs needs --steps >= 1")
+        torch.cuda.synchronize()
+        dump_outputs(a.dump_outputs, last)
     if per_launch_events:
         # march time per frame and launches on this process's GPU(s): one-process groups report every
         # part (the max is the slowest GPU), torchrun ranks their own
@@ -381,7 +433,7 @@ def main():
     # DESIGN section 7's predicted table (the driver's SCALE line has no other view of the link)
     peer_traffic = read_peer_traffic(r, traffic_parts, n_gpus, group, dist, device, backend, world)
     kernel_ms_local = frame_ms_device
-    if n_gpus == 1:
+    if n_gpus == 1 and a.full:
         # the march kernel's own mean launch duration (what rocprofv3 --kernel-trace reports): libvr's
         # per-launch HIP event pairs on each launch's stream, in an untimed pass of the same batches
         # (with two frames in flight launches overlap: a launch lasts longer than a frame's share)
@@ -417,14 +469,14 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / a.steps * 1e3
         mrays = W * H * a.steps / elapsed / 1e6
-        n_in = r.count_samples(p, cam)
+        n_in = r.count_samples(p, cam) if a.full else None   # (a counting frame: a run of its own)
         # the work the march actually did (roofline numerator): class gathers that touched memory
         # (1 B each) and samples evaluated, from the counting instantiation of the same kernel
         # variant over the same frame (vr_count_marched; outside the timed region)
         # (vr_count_work: VRC or TEST, the bytes at each gather's own width)
-        work = r.count_work(p, cam)
+        work = r.count_work(p, cam) if a.full else {"gathers": None, "samples": None, "bytes": None}
         gathers, evaluated, gbytes = work["gathers"], work["samples"], work["bytes"]
-        model_frame = 4 * n_in + 16 * W * H                           # SURVEY 8(d), exact march
+        model_frame = 4 * n_in + 16 * W * H if n_in is not None else None   # SURVEY 8(d), exact march
         frame_write = 16 * W * H   # the launch's one certain HBM traffic (lower bound)
         # rank 0's march launches per frame (N > 1: its share of the frame's tiles)
         lpf = launches_rank0 / a.steps
@@ -495,6 +547,7 @@ def main():
             "n_gpus": n_gpus,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": bool(a.full),
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": "strong",
@@ -560,8 +613,9 @@ def main():
                 "marched_bytes_per_frame": marched_bytes,
                 "achieved_marched": round(achieved_marched, 2) if achieved_marched is not None else None,
                 "frac_marched": round(achieved_marched / HBM_PEAK_GBS, 5) if achieved_marched is not None else None,
-                "model_bytes_per_frame": int(model_frame * share),
-                "model_gbs": round(model_frame * share / (frame_ms_device * 1e-3) / 1e9, 1),
+                "model_bytes_per_frame": int(model_frame * share) if model_frame is not None else None,
+                "model_gbs": (round(model_frame * share / (frame_ms_device * 1e-3) / 1e9, 1)
+                              if model_frame is not None else None),
                 "note": "frac = achieved / peak on the step basis (the counters' bytes of rank 0's march launches "
                         "in one frame over the frame's device time), so every figure follows from the timed "
                         "run; kernel_ms_mean / frac_per_launch are per-launch secondaries.  frac_marched is the "

@@ -112,3 +112,27 @@ def test_design7_prediction_model():
             prev = p["mrays"]
         gain[name] = prev / one["mrays"]
     assert gain["c5"] > gain["c4"] > gain["c3"] >= 1.0
+
+
+def test_dump_outputs_whole_frame_or_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs writes a frame that fits whole; a larger one as the same seeded pixel sample
+    every time, with the pixels' flat indices beside it, within the byte budget."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    W, H = 37, 21
+    frame = torch.arange(W * H * 4, dtype=torch.float32).reshape(W, H, 4)
+    bench.dump_outputs(str(tmp_path / "whole"), frame)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["frame.npy"]
+    got = np.load(tmp_path / "whole" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 24 * 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frame)
+    sa, ia = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "a" / "frame_pixels.npy")
+    assert sa.dtype == np.float32 and sa.shape == (100, 4) and ia.dtype == np.float64 and ia.shape == (100,)
+    assert sa.nbytes + ia.nbytes <= 24 * 100
+    assert np.all(np.diff(ia) > 0) and ia[0] >= 0 and ia[-1] < W * H
+    assert np.array_equal(sa, frame.numpy().reshape(-1, 4)[ia.astype(np.int64)])
+    assert np.array_equal(sa, np.load(tmp_path / "b" / "frame.npy"))
+    assert np.array_equal(ia, np.load(tmp_path / "b" / "frame_pixels.npy"))

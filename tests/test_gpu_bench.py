@@ -64,7 +64,7 @@ def test_one_gpu_accounting_follows_from_the_timed_run():
     """--steps 20 with batches of 8 (20 mod 8 != 0): the event window holds all 20 frames, the device
     time per step (one event pair inside the wall-clock window) is at most the wall time per step,
     frac is bytes per frame over that time, and frac_marched is the counted work over the same time."""
-    r = bench(["--steps", "20", "--warmup", "5", "--cpu-baseline", "0", "--extra", "0"])
+    r = bench(["--full", "--steps", "20", "--warmup", "5", "--cpu-baseline", "0", "--extra", "0"])
     L = line_of(r)
     rf = L["roofline"]
     assert L["n_gpus"] == 1 and L["config"]["parallelism"] == "single-gpu"
@@ -87,7 +87,8 @@ def test_c4_extra_one_gpu():
     """BASELINE configs[3] (512^3, 1920x1080, S = 1024, ESS + ERT) rides the bench line as
     extra.c4 under the headline's kind of context: its own timed region, ranks_rendering, and one
     frame bitwise equal to a fresh one-GPU context's vr_render."""
-    r = bench(["--steps", "6", "--warmup", "2", "--cpu-baseline", "0", "--extra", "0", "--extra-configs", "c4"])
+    r = bench(["--full", "--steps", "6", "--warmup", "2", "--cpu-baseline", "0", "--extra", "0", "--extra-configs",
+               "c4"])
     L = line_of(r)
     c4 = L["extra"]["c4"]
     assert "error" not in c4 and "skipped" not in c4, c4
@@ -101,7 +102,7 @@ def test_c4_extra_two_part_group():
     """The same extra through a one-process two-part group (--devices 0,0: the N-part plan with the
     peer-copy transport): per-rank tiles and march times, the rank-0 weight tuned by measurement, and
     the farmed frame bitwise equal to a one-GPU context's."""
-    r = bench(["--gpus", "2", "--devices", "0,0", "--steps", "6", "--warmup", "2", "--cpu-baseline", "0",
+    r = bench(["--full", "--gpus", "2", "--devices", "0,0", "--steps", "6", "--warmup", "2", "--cpu-baseline", "0",
                "--extra", "0", "--extra-configs", "c4", "--rank0-weights", "1,3"])
     L = line_of(r)
     c4 = L["extra"]["c4"]
@@ -118,7 +119,7 @@ def test_peer_traffic_fields_two_part_group():
     (vr_group_traffic_read), to compare with DESIGN section 7's prediction.  An even deal (weight 1,
     no tuning) over a two-part group: rank 1 sends its tiles' compact RGB, 64 x 64 x 12 B each, every
     frame; rank 0 sends nothing and receives exactly what rank 1 sent; the C4 extra carries the same."""
-    r = bench(["--gpus", "2", "--devices", "0,0", "--steps", "8", "--warmup", "2", "--cpu-baseline", "0",
+    r = bench(["--full", "--gpus", "2", "--devices", "0,0", "--steps", "8", "--warmup", "2", "--cpu-baseline", "0",
                "--extra", "0", "--extra-configs", "c4", "--rank0-weights", "1"])
     L = line_of(r)
     c = L["config"]
@@ -129,3 +130,34 @@ def test_peer_traffic_fields_two_part_group():
         assert sent[0] == 0 and tiles[1] > 0
         assert sent[1] == tiles[1] * 64 * 64 * 12
         assert blk["bytes_into_rank0_per_frame"] == sent[1]
+
+
+def test_plain_run_is_lean_and_dumps_the_last_timed_frame(tmp_path, avg152):
+    """A plain run (no --full) times its steps and nothing else: the fields that take runs of their
+    own are null, the headline fields are there, and --dump-outputs holds the frame the timed path
+    rendered in its last step -- bitwise the frame one vr_render of the same view gives (7 steps in
+    batches of 4: the last frame sits mid-ring)."""
+    import numpy as np
+    import volumerenderingproject_amd as vr
+    W, H, S = 96, 64, 64
+    out = tmp_path / "dump"
+    r = bench(["--gpus", "1", "--steps", "7", "--warmup", "2", "--volume", "avg152", "--width", str(W), "--height",
+               str(H), "--samples", str(S), "--farm-batch", "4", "--dump-outputs", str(out)])
+    L = line_of(r)
+    assert L["full"] is False and L["steps"] == 7 and L["n_gpus"] == 1
+    assert L["value"] > 0 and L["ms_per_step"] > 0 and L["unit"] == "Mrays/s" and L["dtype"] == "f32"
+    # value and ms_per_step are one measurement (ms_per_step is rounded to 1e-4 ms)
+    assert abs(L["value"] - W * H / (L["ms_per_step"] * 1e-3) / 1e6) <= (1e-4 / L["ms_per_step"] + 1e-6) * L["value"]
+    assert L["cpu_baseline"] is None and L["extra"] is None
+    rf = L["roofline"]
+    assert rf["kernel_ms_mean"] is None and rf["samples_marched"] is None and rf["frac_marched"] is None
+    assert L["config"]["n_in_dataset_samples"] is None
+    assert rf["frame_ms_device"] > 0
+    assert sorted(os.listdir(out)) == ["frame.npy"]
+    got = np.load(out / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (W, H, 4)
+    vol, cal = avg152
+    with vr.VolumeRenderer(vol, cal, device=0) as one:
+        ref = one.render(vr.default_params(W, H, S, flags=vr.VR_FLAG_ESS | vr.VR_FLAG_ERT), vr.default_camera(W, H))
+    assert np.array_equal(got, ref)
+    assert float(np.abs(got[..., :3]).max()) > 0   # (not an empty frame)

@@ -51,8 +51,8 @@ def is_march(name):
 def run_pass(counters, bench_args, outdir, tag, rows, timeout=600):
     d = os.path.join(outdir, tag)
     cmd = ["rocprofv3", "--pmc", *counters, "--output-format", "csv", "-d", d, "-o", tag, "--",
-           sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--cpu-baseline", "0",
-           "--traffic-json", "/dev/null", "--extra", "0"] + bench_args
+           sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "1",
+           "--cpu-baseline", "0", "--traffic-json", os.devnull, "--extra", "0"] + bench_args
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=dict(os.environ, TMPDIR="/tmp"))
     if r.returncode != 0:
         sys.stderr.write(r.stdout[-4000:] + r.stderr[-4000:])
