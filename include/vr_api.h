@@ -176,6 +176,14 @@ typedef struct {
                                   change): a transient one-bit-per-leaf occupancy, nleaf^3 / 8 bytes
                                   (2048 leaves: 1 GiB), and 3 nleaf^2 64-bit masks kept (2048: 100 MB;
                                   the MNI shape, 256 leaves: 1.5 MB).  Bitwise the same frames       */
+    /* render */
+    int32_t axis_columns;      /* axis-aligned VRC views (TF(0) transparent, 32-bit offsets, no shading,
+                                  whole float4 frames of a one-GPU context): march every leaf column
+                                  of the visible rectangle once into a column buffer, then copy each
+                                  pixel's column to the frame -- all the pixels over a leaf column get
+                                  the same value bit for bit.  0 = off (one march per pixel), 1 = auto
+                                  (default: when the visible rectangle has at least 2 pixels per
+                                  column), 2 = whenever the scope allows.  Bitwise the same frames    */
 } vr_options;
 
 int vr_options_default(vr_options* out);
@@ -361,7 +369,9 @@ int vr_count_marched(vr_ctx* ctx, const vr_params* params, const vr_camera* came
  * the bytes they read at their own widths (VRC: 1 B per class byte, 16 B per batch of run words;
  * TEST: 2 / 4 / 8 B per corner-volume entry, 4 B per corner-row dword, 32 B per z-window of the axis
  * march) and the samples evaluated.  The same kernel variant as vr_render, in its counting
- * instantiation (atomics per ray): never inside a timed region. */
+ * instantiation (atomics per ray): never inside a timed region.  The counts are those of the per-ray
+ * march -- one march per pixel -- whatever vr_options.axis_columns is: a frame the column path renders
+ * marches each leaf column once instead, which these functions (and vr_count_marched) do not count. */
 typedef struct {
     uint64_t gathers;
     uint64_t bytes;
@@ -369,6 +379,13 @@ typedef struct {
     uint64_t reserved;
 } vr_work_count;
 int vr_count_work(vr_ctx* ctx, const vr_params* params, const vr_camera* camera, vr_work_count* out);
+
+/* What vr_render / vr_render_batch (device frames) would do with vr_options.axis_columns for this
+ * frame, decided on the host alone (no GPU work): out[0] = 1 if the frame takes the column path,
+ * else 0; out[1], out[2] = the leaf columns of the visible rectangle on the view's two fixed axes
+ * (ascending; 0 when the view is not axis-aligned or nothing is visible); out[3] = the pixels of the
+ * visible rectangle. */
+int vr_axis_columns_plan(vr_ctx* ctx, const vr_params* params, const vr_camera* camera, int32_t out[4]);
 
 int vr_synchronize(vr_ctx* ctx);
 /* Use an external HIP stream (hipStream_t passed as void*); NULL restores the ctx's own.  Work on the

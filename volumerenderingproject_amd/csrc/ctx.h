@@ -170,6 +170,11 @@ struct vr_ctx {
         int words = 0;
     };
     std::map<hipStream_t, ZTab> ztabs;   // per stream, like axtab
+    // axis-aligned views' column path (vr_options.axis_columns): the column buffer of the frame in
+    // flight on each stream (float4 per leaf column of its rectangle), per stream like axtab
+    std::map<hipStream_t, vr::DevBuf> colbufs;
+    // vr_render_batch: the column buffers of a call's frames back to back (premarch_columns)
+    vr::DevBuf colbatch;
     int occ_lo[3] = {0, 0, 0}, occ_hi[3] = {-1, -1, -1};   // occupied macro-cell range per axis
     // per axis a: summed-area table over the (a0, a1) plane (the other two axes, ascending) of the
     // cell columns along a holding an occupied cell, (ncell + 1)^2 entries (farm-tile cull of
@@ -240,10 +245,20 @@ void drain_timing(vr_ctx* c);
 void frames_in_flight(vr_ctx* c, int n, const std::function<void(int)>& launch);
 WorkCache* work_for_subset(vr_ctx* c, int W, int H, int tile, const std::vector<int32_t>& own,
                            const std::vector<int32_t>& visible);
+// A frame's leaf-column rectangle [i0, i0 + n0) x [i1, i1 + n1), marched already into buf
+// (vr_render_batch marches the columns of a call's frames in one launch; launch_frame then only expands)
+struct ColumnSlice {
+    const float4* buf;
+    int i0, i1, n0, n1;
+};
+// rect: the visible tile rectangle wc was built for -- given by the whole-frame renders of a one-GPU
+// context only, which may then take the axis views' column path (axis_columns_plan)
 void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, WorkCache* wc, float4* out, int out_tiles,
-                  int tile_w, int tile_h, int out_rgb = 0);
+                  int tile_w, int tile_h, int out_rgb = 0, const TileRect* rect = nullptr,
+                  const ColumnSlice* pre = nullptr);
 void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const WorkView& wv, float4* out, int out_tiles,
-                  int tile_w, int tile_h, int out_rgb = 0);
+                  int tile_w, int tile_h, int out_rgb = 0, const TileRect* rect = nullptr,
+                  const ColumnSlice* pre = nullptr);
 // the multi-GPU plan kernel (vr_kernels.hip plan_kernel): per frame of a batch, this part's work list
 // and (rank 0) the scatter map of the peers' tiles, from the frame's tile owners
 hipError_t launch_plan(const int8_t* owner, int n_frames, int ntiles, int nty, int W, int H, int tile, int rank,

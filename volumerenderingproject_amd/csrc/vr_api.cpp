@@ -38,6 +38,9 @@ hipError_t launch_vrc_march(const VrcFrame&, const WorkTile*, const int32_t*, in
                             const int32_t*, const int64_t*, const uint32_t*, const float4*, int, float4*,
                             hipStream_t, int, const float*, const int32_t*, const unsigned long long*,
                             const uint8_t*, const int32_t*, int32_t*, unsigned long long*);
+hipError_t launch_vrc_columns(const VrcFrame*, int, int, const uint8_t*, const int32_t*, const float4*, int, float4*,
+                              hipStream_t, int, const unsigned long long*, const int32_t*, int32_t*);
+hipError_t launch_axis_expand(const VrcFrame&, const WorkTile*, int, const float4*, float4*, hipStream_t);
 size_t vrc_axis1_table_bytes(const VrcFrame&, int);
 int vrc_batch_of(const VrcFrame&, int);
 hipError_t launch_vrc_stats(const VrcFrame&, const WorkTile*, const int32_t*, int, const uint8_t*, const int32_t*,
@@ -155,6 +158,8 @@ void retire_stream_caches(vr_ctx* c, const hipStream_t* only) {
             v.push_back(&kv.second.buf);
             hosts.push_back(std::move(kv.second.host));
         }
+    for (auto& kv : c->colbufs)
+        if (pick(kv.first)) v.push_back(&kv.second);
     retire_buffers(c, v, &hosts);
     auto drop = [&](auto& m) {
         for (auto it = m.begin(); it != m.end();) it = pick(it->first) ? m.erase(it) : std::next(it);
@@ -162,6 +167,7 @@ void retire_stream_caches(vr_ctx* c, const hipStream_t* only) {
     drop(c->axtab);
     drop(c->frame_lists);
     drop(c->ztabs);
+    drop(c->colbufs);
 }
 // per-stream caches kept for at most this many streams (then the other streams' are retired)
 constexpr size_t kMaxStreamCaches = 8;
@@ -525,6 +531,7 @@ void check_options(const vr_options& o) {
     if (o.table_split != 0 && o.table_split != 1) throw Error(VR_EINVAL, "vr_options: table_split must be 0 or 1");
     if (o.test_corners < 0 || o.test_corners > 3) throw Error(VR_EINVAL, "vr_options: test_corners must be 0..3");
     if (o.leaf_columns < 0 || o.leaf_columns > 1) throw Error(VR_EINVAL, "vr_options: leaf_columns must be 0 or 1");
+    if (o.axis_columns < 0 || o.axis_columns > 2) throw Error(VR_EINVAL, "vr_options: axis_columns must be 0, 1 or 2");
     if (o.farm_tile <= 0 || o.farm_tile % kWgRaysX || o.farm_tile > 4096)
         throw Error(VR_EINVAL, "vr_options: farm_tile must be a positive multiple of 16");
     if (!(o.farm_rank0_weight > 0.0f && o.farm_rank0_weight <= 1e9f))
@@ -1357,18 +1364,143 @@ TestFrame make_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam) {
     return f;
 }
 
+// make_vrc plus what the march's launch adds to it from the context: the exact frames' empty-space
+// skipping, the class volume this view marches and its addressing, run words and the split view table
+// (everything but the work list and the output, which launch_frame sets)
+VrcFrame make_vrc_march(const vr_ctx* c, const vr_params* p, const vr_camera* cam) {
+    VrcFrame f = make_vrc(c, p, cam);
+    // exact back-to-front frames march with empty-space skipping: skipping an alpha-0 sample is
+    // bitwise exact back to front (r * (1 - 0) + c * 0 = r, the reference's blend).  Axis-aligned
+    // views: column masks (C3 82 -> 61 us, C5 5.37 -> 2.68 ms); general orthographic views: the
+    // lazy cell-distance test (oblique 90 -> 87 us).  Conic views and TEST keep the plain march.
+    if (c->opt.exact_skip && !(f.flags & (VR_FLAG_ESS | VR_FLAG_ERT | VR_FLAG_SHADE)) && !f.conic &&
+        f.zero_transparent)
+        f.flags |= VR_FLAG_ESS;
+    // the volume this view marches: general views of a compact 32-bit volume take its byte copy
+    const bool use_gen = c->gen && f.axis1 < 0;
+    const int cb = use_gen ? 8 : c->cbits;
+    const int64_t vbytes = use_gen ? c->gen_bytes : c->cls_bytes;
+    f.cls_bytes = c->idx64 ? 0 : (int32_t)vbytes;
+    // class addressing: bits (o >> 3, bit o & 7) below 8 bits per class, bytes at 8
+    f.cbits = cb;
+    f.osh = cb < 8 ? 3 : 0;
+    f.omask = cb < 8 ? 7 : 0;
+    f.mapout_ok = (cb < 8 ? vbytes * 8 : vbytes) < ((int64_t)1 << 29) ? 1 : 0;
+    // run words (views along z): 8-byte words of the class volume, whose bytes are a multiple of 8
+    // (128-byte default bricks) so every word lies inside it
+    f.qsh = cb < 8 ? 6 : 3;
+    f.bsh = cb < 8 ? 0 : 3;
+    f.zrun = (f.axis1 == 2 && vbytes % 8 == 0 &&
+              (c->opt.run_words == 2 || (c->opt.run_words == 0 && c->idx64))) ? 1 : 0;
+    // a batch's K samples advance |step_z| 2^D leaves each: the leaf index moves at most
+    // floor((K - 1) |step_z| 2^D + 1) over the batch (a tiny margin for the per-sample roundings),
+    // the voxel index as much when L = 2^D (the leaf map is a shift) or one more than the scaled
+    // leaf span otherwise; a voxel span of at most bz touches at most two z-bricks.  Two z-bricks
+    // are two WORDS only when every z-run lies inside one aligned 8-byte word: runs start at
+    // multiples of their length bz * cb bits (bricks are contiguous), so that needs bz * cb to
+    // divide 64 (e.g. not bz = 16 at 8 bits, nor bz = 3, 5, 6); otherwise the batch keeps the
+    // per-sample miss test
+    if (f.zrun) {
+        const double dl = std::fabs((double)f.step[2]) * (double)c->oct.nleaf;
+        const double leaf_span =
+            std::floor((double)(vrc_batch_of(f, c->batch) - 1) * dl * (1.0 + 1e-6) + 1.0 + 1e-4);
+        const double L = (double)c->oct.longest_dimension;
+        const double vox_span = (L == (double)c->oct.nleaf) ? leaf_span
+                                                            : std::floor(leaf_span * L / (double)c->oct.nleaf) + 1.0;
+        const int run_bits = c->brick[2] * cb;
+        f.zspan2 = (vox_span <= (double)c->brick[2] && run_bits <= 64 && 64 % run_bits == 0) ? 1 : 0;
+    }
+    f.c0_noop = (!c->tf.empty() && c->tf[0].rgba[3] == 0.0f) ? 1 : 0;
+    // split view table (views along z, 32-bit volumes): the rays' (x, y) offsets are whole bytes
+    // when a brick's z-run is (build_layout: bz * cbits a multiple of 8)
+    f.tsplit = (f.axis1 == 2 && !c->idx64 && !f.zrun && !(f.flags & VR_FLAG_SHADE) && c->opt.table_split &&
+                (cb == 8 || (c->brick[2] * cb) % 8 == 0)) ? 1 : 0;
+    return f;
+}
+
+// The column path of an axis-aligned view (vr_options.axis_columns; vr_kernels.hip axis_expand_kernel).
+// Scope: an AXIS1 VRC frame f (orthographic along a volume axis, not conic) with TF(0) transparent,
+// 32-bit class offsets, no shading, a non-zero step and no counting pass, rendered whole by a
+// one-GPU context (rect: the visible tile rectangle of that render).  The leaf-column rectangle is
+// the range of the kernel's own leaf indices (axis_leaf_column, restated here in float) over the
+// four corners of the visible pixel rectangle -- the index is monotone in x and in y separately,
+// every float operation being monotone -- widened by one leaf each way and clamped to the leaf range:
+// conservative, never short.  A pixel outside the cube is not bound by it (the expand pass stores
+// the background there).  Auto (axis_columns = 1) takes the path when the visible rectangle has at
+// least kAxisColumnsRatio pixels per column: below that the column march is no smaller than the
+// per-pixel one and the expand pass is pure overhead.
+constexpr int64_t kAxisColumnsRatio = 2;
+struct ColumnPlan {
+    bool take = false;
+    int i0 = 0, i1 = 0, n0 = 0, n1 = 0;   // rectangle [i0, i0 + n0) x [i1, i1 + n1) on the fixed axes a0 < a1
+    int64_t pixels = 0;                   // of the visible rectangle
+};
+ColumnPlan axis_columns_plan(const vr_ctx* c, const vr_params* p, const VrcFrame& f, const TileRect& rect) {
+    ColumnPlan cp;
+    const int W = p->width, H = p->height;
+    int x0 = 0, x1 = W - 1, y0 = 0, y1 = H - 1;
+    if (!rect.all) {
+        if (rect.tx1 < rect.tx0 || rect.ty1 < rect.ty0) return cp;   // nothing visible
+        x0 = rect.tx0 * kWgRaysX; x1 = std::min(W, (rect.tx1 + 1) * kWgRaysX) - 1;
+        y0 = rect.ty0 * kWgRaysY; y1 = std::min(H, (rect.ty1 + 1) * kWgRaysY) - 1;
+    }
+    cp.pixels = (int64_t)(x1 - x0 + 1) * (y1 - y0 + 1);
+    if (p->mode != VR_MODE_VRC || f.axis1 < 0 || f.conic) return cp;
+    const int ma = f.axis1, a0 = ma == 0 ? 1 : 0, a1 = ma == 2 ? 1 : 2;
+    const int nleaf = f.nleaf;
+    int lo[2] = {nleaf, nleaf}, hi[2] = {-1, -1};
+    for (int k = 0; k < 4; ++k) {
+        const int x = (k & 1) ? x1 : x0, y = (k & 2) ? y1 : y0;
+        const float A = (float)x * f.rsw / (float)f.W;
+        const float B = (float)y * f.rsh / (float)f.H;
+        const int ax[2] = {a0, a1};
+        for (int j = 0; j < 2; ++j) {
+            const float P0 = (f.tlc[ax[j]] + A * f.right[ax[j]]) + B * (-f.up[ax[j]]);
+            const float v = (P0 + 0.5f) * f.leaves;
+            // (the kernel's clamped index wherever the pixel is inside the cube; monotone everywhere)
+            const int i = v >= 0.0f ? (v < (float)nleaf ? (int)v : nleaf - 1) : 0;
+            lo[j] = std::min(lo[j], i); hi[j] = std::max(hi[j], i);
+        }
+    }
+    for (int j = 0; j < 2; ++j) { lo[j] = std::max(0, lo[j] - 1); hi[j] = std::min(nleaf - 1, hi[j] + 1); }
+    cp.i0 = lo[0]; cp.i1 = lo[1];
+    cp.n0 = hi[0] - lo[0] + 1; cp.n1 = hi[1] - lo[1] + 1;
+    const int64_t cols = (int64_t)cp.n0 * cp.n1;
+    const bool scope = c->opt.axis_columns != 0 && f.zero_transparent && !c->idx64 && !(f.flags & VR_FLAG_SHADE) &&
+                       f.step[ma] != 0.0f && !c->count_ptr && !c->group && !c->part_of && cols <= ((int64_t)1 << 26);
+    cp.take = scope && (c->opt.axis_columns == 2 || cp.pixels >= kAxisColumnsRatio * cols);
+    return cp;
+}
+
+// The column march's frame of a frame f that takes the column path with plan cp: the leaf-column
+// rectangle as a col_n0 x col_n1 "frame" of 16 x 16 tiles, one workgroup each in 8 equal chunks
+// (one per XCD: vrc_march_kernel, COLS), no work list, no background-only workgroups
+VrcFrame column_frame(const VrcFrame& f, const ColumnPlan& cp) {
+    VrcFrame fc = f;
+    fc.W = cp.n0; fc.H = cp.n1;
+    fc.col_i0 = cp.i0; fc.col_i1 = cp.i1; fc.col_n0 = cp.n0; fc.col_n1 = cp.n1;
+    const int tiles = ((cp.n0 + kWgRaysX - 1) / kWgRaysX) * ((cp.n1 + kWgRaysY - 1) / kWgRaysY);
+    fc.n_work = tiles;
+    fc.n_slots = 8 * ((tiles + 7) / 8);
+    fc.persist_wgs = 0;
+    fc.out_tiles = 0; fc.out_rgb = 0;
+    fc.bg_first = INT32_MAX;
+    fc.bg_group = 1;
+    return fc;
+}
+
 void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, WorkCache* wc, float4* out, int out_tiles,
-                  int tile_w, int tile_h, int out_rgb) {
+                  int tile_w, int tile_h, int out_rgb, const TileRect* rect, const ColumnSlice* pre) {
     WorkView wv;
     wv.work = wc->work.as<WorkTile>();
     wv.n_work = wc->n_work;
     wv.n_blocks = wc->n_blocks;
     wv.bg_first = wc->bg_first;
-    launch_frame(c, p, cam, wv, out, out_tiles, tile_w, tile_h, out_rgb);
+    launch_frame(c, p, cam, wv, out, out_tiles, tile_w, tile_h, out_rgb, rect, pre);
 }
 
 void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const WorkView& wv, float4* out, int out_tiles,
-                  int tile_w, int tile_h, int out_rgb) {
+                  int tile_w, int tile_h, int out_rgb, const TileRect* rect, const ColumnSlice* pre) {
     const WorkView* wc = &wv;
     if (wc->n_blocks == 0) return;
     std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
@@ -1389,14 +1521,7 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             c->nrm.ensure((size_t)n * sizeof(float4));
             hip_check(launch_normals(c->vol.as<float>(), c->d[0], c->d[1], c->d[2], c->nrm.as<float4>(), c->stream));
         }
-        VrcFrame f = make_vrc(c, p, cam);
-        // exact back-to-front frames march with empty-space skipping: skipping an alpha-0 sample is
-        // bitwise exact back to front (r * (1 - 0) + c * 0 = r, the reference's blend).  Axis-aligned
-        // views: column masks (C3 82 -> 61 us, C5 5.37 -> 2.68 ms); general orthographic views: the
-        // lazy cell-distance test (oblique 90 -> 87 us).  Conic views and TEST keep the plain march.
-        if (c->opt.exact_skip && !(f.flags & (VR_FLAG_ESS | VR_FLAG_ERT | VR_FLAG_SHADE)) && !f.conic &&
-            f.zero_transparent)
-            f.flags |= VR_FLAG_ESS;
+        VrcFrame f = make_vrc_march(c, p, cam);
         f.out_tiles = out_tiles; f.tile_w = tile_w; f.tile_h = tile_h; f.n_work = wc->n_work; f.out_rgb = out_rgb;
         f.n_slots = wc->n_blocks;
         f.persist_wgs = c->persist_wgs;
@@ -1411,45 +1536,7 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             n_launch = wc->bg_first + (wc->n_work - wc->bg_first + kBgGroup - 1) / kBgGroup;
             f.n_slots = n_launch;
         }
-        // the volume this view marches: general views of a compact 32-bit volume take its byte copy
-        const bool use_gen = c->gen && f.axis1 < 0;
-        const int cb = use_gen ? 8 : c->cbits;
-        const int64_t vbytes = use_gen ? c->gen_bytes : c->cls_bytes;
-        f.cls_bytes = c->idx64 ? 0 : (int32_t)vbytes;
-        // class addressing: bits (o >> 3, bit o & 7) below 8 bits per class, bytes at 8
-        f.cbits = cb;
-        f.osh = cb < 8 ? 3 : 0;
-        f.omask = cb < 8 ? 7 : 0;
-        f.mapout_ok = (cb < 8 ? vbytes * 8 : vbytes) < ((int64_t)1 << 29) ? 1 : 0;
-        // run words (views along z): 8-byte words of the class volume, whose bytes are a multiple of 8
-        // (128-byte default bricks) so every word lies inside it
-        f.qsh = cb < 8 ? 6 : 3;
-        f.bsh = cb < 8 ? 0 : 3;
-        f.zrun = (f.axis1 == 2 && vbytes % 8 == 0 &&
-                  (c->opt.run_words == 2 || (c->opt.run_words == 0 && c->idx64))) ? 1 : 0;
-        // a batch's K samples advance |step_z| 2^D leaves each: the leaf index moves at most
-        // floor((K - 1) |step_z| 2^D + 1) over the batch (a tiny margin for the per-sample roundings),
-        // the voxel index as much when L = 2^D (the leaf map is a shift) or one more than the scaled
-        // leaf span otherwise; a voxel span of at most bz touches at most two z-bricks.  Two z-bricks
-        // are two WORDS only when every z-run lies inside one aligned 8-byte word: runs start at
-        // multiples of their length bz * cb bits (bricks are contiguous), so that needs bz * cb to
-        // divide 64 (e.g. not bz = 16 at 8 bits, nor bz = 3, 5, 6); otherwise the batch keeps the
-        // per-sample miss test
-        if (f.zrun) {
-            const double dl = std::fabs((double)f.step[2]) * (double)c->oct.nleaf;
-            const double leaf_span =
-                std::floor((double)(vrc_batch_of(f, c->batch) - 1) * dl * (1.0 + 1e-6) + 1.0 + 1e-4);
-            const double L = (double)c->oct.longest_dimension;
-            const double vox_span = (L == (double)c->oct.nleaf) ? leaf_span
-                                                                : std::floor(leaf_span * L / (double)c->oct.nleaf) + 1.0;
-            const int run_bits = c->brick[2] * cb;
-            f.zspan2 = (vox_span <= (double)c->brick[2] && run_bits <= 64 && 64 % run_bits == 0) ? 1 : 0;
-        }
-        f.c0_noop = (!c->tf.empty() && c->tf[0].rgba[3] == 0.0f) ? 1 : 0;
-        // split view table (views along z, 32-bit volumes): the rays' (x, y) offsets are whole bytes
-        // when a brick's z-run is (build_layout: bz * cbits a multiple of 8)
-        f.tsplit = (f.axis1 == 2 && !c->idx64 && !f.zrun && !(f.flags & VR_FLAG_SHADE) && c->opt.table_split &&
-                    (cb == 8 || (c->brick[2] * cb) % 8 == 0)) ? 1 : 0;
+        const bool use_gen = c->gen && f.axis1 < 0;   // (make_vrc_march: the volume this view marches)
         const uint8_t* vcls = use_gen ? c->cls_gen.as<uint8_t>() : c->cls_vrc.as<uint8_t>();
         // general 32-bit views stage their LDS maps from the kMapPadMax-padded copy (vrc_march_kernel)
         const bool gen_view = f.axis1 < 0 || f.conic;
@@ -1462,7 +1549,7 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
         const int32_t* gtab = nullptr;
         int32_t* gtab_out = nullptr;
         std::vector<uint32_t> pub_key;
-        if (c->tab_reuse && f.axis1 >= 0 && !f.conic) {
+        if (c->tab_reuse && f.axis1 >= 0 && !f.conic && !pre) {   // (pre: no march in this call)
             const int ma = f.axis1;
             const float kf[] = {f.sd, f.fc, f.tlc[ma], f.right[ma], f.up[ma], f.front[ma], f.step[ma], f.leaves};
             const int ki[] = {ma, f.S, f.flags, f.zero_transparent, c->batch, f.ncell, f.cb_shift, f.tsplit, f.zrun, f.cbits};
@@ -1521,6 +1608,31 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             }
         }
 #endif
+        ColumnPlan cp;
+        if (!pre && rect && !out_tiles && !out_rgb) cp = axis_columns_plan(c, p, f, *rect);
+        if (pre) {   // the frame's columns are marched already (vr_render_batch, premarch_columns): expand only
+            f.col_i0 = pre->i0; f.col_i1 = pre->i1; f.col_n0 = pre->n0; f.col_n1 = pre->n1;
+            hip_check(launch_axis_expand(f, wc->work, n_launch, pre->buf, out, c->stream));
+        } else if (cp.take) {
+            // column march into this stream's column buffer, then the expand pass, in stream order: the
+            // next frame of the stream overwrites the buffer only after this frame's expand has read it.
+            // A buffer that must grow is retired behind the work queued so far, not freed under it.
+            const size_t need = (size_t)cp.n0 * cp.n1 * sizeof(float4);
+            if (c->colbufs.size() >= kMaxStreamCaches && !c->colbufs.count(c->stream)) retire_stream_caches(c, nullptr);
+            DevBuf& cb = c->colbufs[c->stream];
+            if (need > cb.bytes) {
+                if (cb.p) retire_buffers(c, {&cb});
+                cb.ensure(need + need / 4);
+            }
+            const VrcFrame fc = column_frame(f, cp);
+            const int grid = fc.n_slots;
+            hip_check(launch_vrc_columns(&fc, 1, grid, vcls, vmaps, c->tf_rgba.as<float4>(), (int)c->tf.size(),
+                                         cb.as<float4>(), c->stream, c->batch,
+                                         (c->leafcols ? c->occ_leafcols : c->occ_cols).as<unsigned long long>(), gtab,
+                                         gtab_out));
+            f.col_i0 = cp.i0; f.col_i1 = cp.i1; f.col_n0 = cp.n0; f.col_n1 = cp.n1;
+            hip_check(launch_axis_expand(f, wc->work, n_launch, cb.as<float4>(), out, c->stream));
+        } else
         hip_check(launch_vrc_march(f, wc->work, nullptr, n_launch, vcls, vmaps,
                                    c->idx64 ? c->pmapx64.as<int64_t>() : nullptr, c->occ.as<uint32_t>(),
                                    c->tf_rgba.as<float4>(), (int)c->tf.size(), out, c->stream, c->batch,
@@ -1685,6 +1797,8 @@ void destroy_ctx_single(vr_ctx* c) {
     c->slot_maps.clear();
     c->axtab.clear();
     c->ztabs.clear();
+    c->colbufs.clear();
+    c->colbatch.reset();
     for (auto* v : {&c->ev_free, &c->ev_pending})
         for (auto& ev : *v) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1798,6 +1912,7 @@ int vr_options_default(vr_options* o) {
     // launch at the same frame time, before the plane table)
     o->test_corners = 0;
     o->leaf_columns = 1;   // C3 default view
+    o->axis_columns = 1;
     return VR_OK;
 }
 
@@ -1886,7 +2001,7 @@ int vr_render(vr_ctx* c, const vr_params* p, const vr_camera* cam, float* out, i
             c->frame.ensure(bytes);
             dst = c->frame.as<float4>();
         }
-        launch_frame(c, p, cam, wc, dst, 0, 0, 0);
+        launch_frame(c, p, cam, wc, dst, 0, 0, 0, 0, &rect);
         if (!out_on_device) {
             hip_check(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, c->stream));
             hip_check(hipStreamSynchronize(c->stream));
@@ -1895,6 +2010,53 @@ int vr_render(vr_ctx* c, const vr_params* p, const vr_camera* cam, float* out, i
         }
         return VR_OK;
     });
+}
+
+// vr_render_batch, column path: the column marches of the call's frames, kColBatch frames to a launch
+// (grid y = frame), on the ctx stream before the frames fork over the in-flight streams; each frame's
+// launch is then its expand pass alone.  A frame's column march is a few hundred workgroups of
+// latency-bound rays -- about as long alone as a whole per-pixel march -- and a second launch per
+// frame costs the host as much as the first: together the marches fill the GPU, at a sixth of a launch
+// per frame.  The frames taken are those in axis_columns_plan's scope that share the first one's
+// kernel variant (view axis, table form); the others keep their own march in launch_frame.
+// pre[i].buf is null for those.  The call's column buffer is reused call after call in stream order
+// (the call's last join puts every expand before the next call's march).
+void premarch_columns(vr_ctx* c, const vr_params* p, const vr_camera* cams, int n, const std::vector<TileRect>& rects,
+                      std::vector<ColumnSlice>& pre) {
+    pre.assign((size_t)n, ColumnSlice{nullptr, 0, 0, 0, 0});
+    if (n < 2 || c->opt.axis_columns == 0 || p->mode != VR_MODE_VRC || c->timing) return;
+    std::vector<VrcFrame> fcs;
+    std::vector<int> idx;
+    int64_t total = 0;
+    int grid = 0;
+    for (int i = 0; i < n; ++i) {
+        const VrcFrame f = make_vrc_march(c, p, &cams[i]);
+        const ColumnPlan cp = axis_columns_plan(c, p, f, rects[(size_t)i]);
+        if (!cp.take) continue;
+        VrcFrame fc = column_frame(f, cp);
+        if (!fcs.empty() && (fc.axis1 != fcs[0].axis1 || fc.tsplit != fcs[0].tsplit || fc.zrun != fcs[0].zrun)) continue;
+        fc.col_ofs = total;
+        total += ((int64_t)cp.n0 * cp.n1 + 15) & ~(int64_t)15;
+        grid = std::max(grid, fc.n_slots);
+        fcs.push_back(fc);
+        idx.push_back(i);
+    }
+    if (fcs.size() < 2) return;
+    for (VrcFrame& fc : fcs) fc.n_slots = grid;   // (every workgroup of the launch walks its own frame's tiles)
+    const size_t need = (size_t)total * sizeof(float4);
+    if (need > c->colbatch.bytes) {
+        if (c->colbatch.p) retire_buffers(c, {&c->colbatch});
+        c->colbatch.ensure(need + need / 4);
+    }
+    for (size_t k = 0; k < fcs.size(); k += kColBatch)
+        hip_check(launch_vrc_columns(fcs.data() + k, (int)std::min<size_t>(kColBatch, fcs.size() - k), grid,
+                                     c->cls_vrc.as<uint8_t>(), c->pmaps.as<int32_t>(), c->tf_rgba.as<float4>(),
+                                     (int)c->tf.size(), c->colbatch.as<float4>(), c->stream, c->batch,
+                                     (c->leafcols ? c->occ_leafcols : c->occ_cols).as<unsigned long long>(), nullptr,
+                                     nullptr));
+    for (size_t k = 0; k < fcs.size(); ++k)
+        pre[(size_t)idx[k]] = ColumnSlice{c->colbatch.as<float4>() + fcs[k].col_ofs, fcs[k].col_i0, fcs[k].col_i1,
+                                          fcs[k].col_n0, fcs[k].col_n1};
 }
 
 int vr_render_batch(vr_ctx* c, const vr_params* p, const vr_camera* cams, int32_t n_frames, float* out,
@@ -1917,12 +2079,17 @@ int vr_render_batch(vr_ctx* c, const vr_params* p, const vr_camera* cams, int32_
             return VR_OK;
         }
         set_device(c);
+        std::vector<TileRect> rects((size_t)n_frames);
+        if (c->cull)
+            for (int32_t f = 0; f < n_frames; ++f) rects[(size_t)f] = visible_rect(c, p, &cams[f], kWgRaysX, kWgRaysY);
+        std::vector<ColumnSlice> pre;
+        premarch_columns(c, p, cams, n_frames, rects, pre);
         frames_in_flight(c, n_frames, [&](int f) {
-            TileRect rect;
-            if (c->cull) rect = visible_rect(c, p, &cams[f], kWgRaysX, kWgRaysY);
+            const TileRect& rect = rects[(size_t)f];
             WorkCache* wc = c->order_mode == 0 ? frame_list(c, p, &cams[f], rect)
                                                : work_for(c, p->width, p->height, 0, 0, 0, 1, nullptr, &rect);
-            launch_frame(c, p, &cams[f], wc, reinterpret_cast<float4*>(out + (size_t)f * fpx), 0, 0, 0);
+            launch_frame(c, p, &cams[f], wc, reinterpret_cast<float4*>(out + (size_t)f * fpx), 0, 0, 0, 0, &rect,
+                         pre[(size_t)f].buf ? &pre[(size_t)f] : nullptr);
         });
         if (!(out_flags & VR_OUT_ASYNC)) hip_check(hipStreamSynchronize(c->stream));
         return VR_OK;
@@ -2109,6 +2276,9 @@ int vr_count_samples(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64
     });
 }
 
+// Counts the per-ray march -- one march per pixel -- whatever vr_options.axis_columns is: the counting
+// pass never takes the column path (launch_frame without a visible rectangle, and count_ptr is out of
+// axis_columns_plan's scope), and the tests that pin these counts pin that definition.
 int vr_count_work(vr_ctx* c, const vr_params* p, const vr_camera* cam, vr_work_count* out) {
     if (!c || !cam || !out) return VR_EINVAL;
     return guard([&] {
@@ -2152,6 +2322,29 @@ int vr_count_marched(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64
         if (samples) *samples = w.samples;
     }
     return rc;
+}
+
+int vr_axis_columns_plan(vr_ctx* c, const vr_params* p, const vr_camera* cam, int32_t out[4]) {
+    if (!c || !cam || !out) return VR_EINVAL;
+    return guard([&] {
+        check_params(p);
+        out[0] = out[1] = out[2] = out[3] = 0;
+        TileRect rect;
+        if (c->cull) rect = visible_rect(c, p, cam, kWgRaysX, kWgRaysY);
+        if (p->mode != VR_MODE_VRC) {   // (TEST frames: only the visible rectangle's pixels)
+            VrcFrame none;
+            std::memset(&none, 0, sizeof none);
+            none.axis1 = -1;
+            out[3] = (int32_t)std::min<int64_t>(axis_columns_plan(c, p, none, rect).pixels, INT32_MAX);
+            return VR_OK;
+        }
+        const ColumnPlan cp = axis_columns_plan(c, p, make_vrc(c, p, cam), rect);
+        out[0] = cp.take ? 1 : 0;
+        out[1] = cp.n0;
+        out[2] = cp.n1;
+        out[3] = (int32_t)std::min<int64_t>(cp.pixels, INT32_MAX);
+        return VR_OK;
+    });
 }
 
 int vr_frame_to_rgb8(vr_ctx* c, int32_t W, int32_t H, int32_t orientation, const float* d_frame, uint8_t* rgb,

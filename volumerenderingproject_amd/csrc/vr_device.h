@@ -105,7 +105,21 @@ struct VrcFrame {
     // shading (VR_FLAG_SHADE)
     float ka, kd, ks, shininess;
     int32_t d1i, d2i, d3i;        // dims as int for gradient clamping
+    // AXIS1 column path (vr_api.cpp axis_columns_plan): the leaf-column rectangle [col_i0, col_i0 +
+    // col_n0) x [col_i1, col_i1 + col_n1) of the two fixed axes (ascending).  The column march runs
+    // over it as a col_n0 x col_n1 "frame" (W = col_n0, H = col_n1: one lane per leaf column) into the
+    // column buffer, which axis_expand_kernel then copies to the pixels
+    int32_t col_i0, col_i1, col_n0, col_n1;
+    int64_t col_ofs;              // column marches: the frame's first float4 in the launch's column buffer
 };
+
+// The frames whose column marches share one launch (vrc_march_kernel, COLS: grid y = frame), passed by
+// value: with the march's other arguments it stays under the 4 KB a kernel's arguments may take
+constexpr int kColBatch = 6;
+struct ColBatch {
+    VrcFrame f[kColBatch];
+};
+static_assert(sizeof(ColBatch) + 256 <= 4096, "ColBatch must fit the kernel argument segment");
 
 // Per-frame constants of the TEST march (kernel.cu:72-187).
 struct TestFrame {

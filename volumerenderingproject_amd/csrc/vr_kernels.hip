@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstring>
 #include <type_traits>
 
 #include "vr_device.h"
@@ -253,11 +254,8 @@ constexpr int kTfGroup = 4;
 template <bool CONIC>
 __device__ __forceinline__ void ray_setup(const VrcFrame& f, int x, int y, float org[3], float dir[3], float base[3],
                                           float stp[3], float istp[3], int& s_begin, int& s_end) {
-    const float A = (float)x * f.rsw / (float)f.W;
-    const float B = (float)y * f.rsh / (float)f.H;
     float P0[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) P0[c] = (f.tlc[c] + A * f.right[c]) + B * (-f.up[c]);
+    ray_origin(f, x, y, P0);
     if (CONIC) {
         const float D[3] = {P0[0] - f.campos[0], P0[1] - f.campos[1], P0[2] - f.campos[2]};
         const float inv = 1.0f / sqrtf((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2]);   // glm::normalize
@@ -293,6 +291,28 @@ __device__ __forceinline__ void ray_setup(const VrcFrame& f, int x, int y, float
             s_begin = max(0, (int)floorf(a) - 1);
             s_end = min(f.S, (int)ceilf(bnd) + 2);
         }
+    }
+}
+
+// Column march of an axis-aligned view (vrc_march_kernel, COLS): the sample range of every ray of the
+// frame that lies over the dataset.  Such a ray's fixed coordinates are inside the dataset box, so
+// ray_setup's clip comes from the march axis ma alone: the same a / bnd arithmetic for component ma,
+// whose origin is ray-independent (right[ma] == up[ma] == 0 add signed zeros, as in axis1_table).
+// Wave-uniform.
+__device__ __forceinline__ void axis_sample_range(const VrcFrame& f, int ma, int& s_begin, int& s_end) {
+    s_begin = 0;
+    s_end = f.S;
+    if (!f.zero_transparent) return;
+    const float org = (f.tlc[ma] + 0.0f * f.right[ma]) + 0.0f * (-f.up[ma]);
+    const float base = (org + f.fc * f.front[ma]) + 0.5f;
+    float a = 0.0f, bnd = (float)(f.S - 1);
+    const float t0 = (f.box_lo[ma] - base) * f.inv_step[ma], t1 = (f.box_hi[ma] - base) * f.inv_step[ma];
+    a = fmaxf(a, fminf(t0, t1));
+    bnd = fminf(bnd, fmaxf(t0, t1));
+    if (a > bnd) { s_end = 0; }
+    else {
+        s_begin = max(0, (int)floorf(a) - 1);
+        s_end = min(f.S, (int)ceilf(bnd) + 2);
     }
 }
 
@@ -434,8 +454,15 @@ __device__ __forceinline__ void axis1_table(const VrcFrame& f, int ma, bool cell
     }
 }
 
-template <bool F2B, bool ESS, bool IDX64, int GEOM, int K, bool SHADE, int STATS = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves<GEOM, ESS, K, SHADE>()))) void vrc_march_kernel(VrcFrame f, const WorkTile* __restrict__ work,
+// The frame argument of vrc_march_kernel: the frame, or for the column march (COLS) the frames of a
+// batch (vr_device.h ColBatch), of which workgroup row blockIdx.y marches one
+template <bool COLS> struct FrameArg { using type = VrcFrame; };
+template <> struct FrameArg<true> { using type = ColBatch; };
+__device__ __forceinline__ const VrcFrame& frame_arg(const VrcFrame& fa) { return fa; }
+__device__ __forceinline__ const VrcFrame& frame_arg(const ColBatch& fa) { return fa.f[blockIdx.y]; }
+
+template <bool F2B, bool ESS, bool IDX64, int GEOM, int K, bool SHADE, int STATS = 0, bool COLS = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves<GEOM, ESS, K, SHADE>()))) void vrc_march_kernel(typename FrameArg<COLS>::type fa, const WorkTile* __restrict__ work,
                                                         const int32_t* __restrict__ order,
                                                         const uint8_t* __restrict__ cls,
                                                         const int32_t* __restrict__ gmaps,
@@ -451,6 +478,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
                                                         const int32_t* __restrict__ gtab,
                                                         int32_t* __restrict__ gtab_out) {
     using idx_t = typename IdxT<IDX64>::type;
+    // COLS: the column marches of up to kColBatch frames in one launch (vr_render_batch), grid y =
+    // frame: every frame's constants are kernel arguments (fa.f[blockIdx.y]: scalar loads at a
+    // wave-uniform offset of the kernarg segment, like the single frame's), its columns stored
+    // f.col_ofs float4s into the call's column buffer
+    const VrcFrame& f = frame_arg(fa);
+    if constexpr (COLS) out += f.col_ofs;
     constexpr bool AXIS1 = GEOM == kGeomAxis1 || GEOM == kGeomAxis1Run || GEOM == kGeomAxis1Z;
     constexpr bool CONIC = GEOM == kGeomConic;
     constexpr bool RUNW = GEOM == kGeomAxis1Run;   // run-word class gathers (host: f.zrun)
@@ -472,9 +505,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
     // tile load is unconditional (index clamped; a background-only workgroup leaves before using it).
     // (`order`, a block -> work-entry indirection, is unused: every caller passes null, and testing
     // it put one more dependent scalar round trip in front of the first load)
-    const int b_first = (int)blockIdx.x;
+    // COLS (column march, AXIS1 only: f.W x f.H is the leaf-column rectangle, `out` the column buffer):
+    // no work list -- the grid is 8 equal chunks of the rectangle's 16 x 16 tiles in x-major order,
+    // chunk blockIdx.x % 8 on its XCD, so each XCD's L2 holds one slab of the class volume
+    int b_first = (int)blockIdx.x;
+    if constexpr (COLS) b_first = (b_first & 7) * ((int)gridDim.x >> 3) + (b_first >> 3);
     const bool b_ok = b_first >= 0 && b_first < f.n_work;
-    WorkTile wt_first = work[b_ok ? b_first : 0];
+    WorkTile wt_first;
+    if constexpr (COLS) {
+        const int nty = (f.H + kWgRaysY - 1) / kWgRaysY;
+        wt_first = WorkTile{(b_first / nty) * kWgRaysX, (b_first % nty) * kWgRaysY, 0, 0};
+    } else {
+        wt_first = work[b_ok ? b_first : 0];
+    }
     if (!b_ok) wt_first = WorkTile{0, 0, 0, 0};
     // the frame constants the exits below branch on, loaded in the first round: left to the
     // compiler, each is loaded (and waited for) inside the branch that first needs it
@@ -539,26 +582,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
     };
     auto init_ray = [&](const WorkTile& wt, Ray& R) {
         ray_of_thread(wt, R.x, R.y);
-        ray_setup<CONIC>(f, R.x, R.y, R.P0, R.dir, R.base, R.stp, R.istp, R.s_begin, R.s_end);
+        if constexpr (COLS) {
+            // a lane's work item is the leaf column (f.col_i0 + x, f.col_i1 + y); the AXIS1 march reads
+            // none of the per-pixel geometry (SHADE, which does, has no column march)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) R.P0[c] = R.dir[c] = R.base[c] = R.stp[c] = R.istp[c] = 0.0f;
+            axis_sample_range(f, ma, R.s_begin, R.s_end);
+        } else {
+            ray_setup<CONIC>(f, R.x, R.y, R.P0, R.dir, R.base, R.stp, R.istp, R.s_begin, R.s_end);
+        }
         R.fixed_off = 0;
         R.fixed_in = true;
         R.colmask = 0;
         if (AXIS1) {
             const int a0 = ma == 0 ? 1 : 0, a1 = ma == 2 ? 1 : 2;
-            const float q0 = (ma == 0 ? R.P0[1] : R.P0[0]) + 0.5f;
-            const float q1 = (ma == 2 ? R.P0[1] : R.P0[2]) + 0.5f;
             // leaf indices clamped so the lookups are unconditional (an out-of-cube axis makes the
             // whole ray TF(0) anyway)
-            const unsigned lim = (unsigned)(f.nleaf - 1);
-            const int i0 = (int)min((unsigned)(int)(q0 * f.leaves), lim);
-            const int i1 = (int)min((unsigned)(int)(q1 * f.leaves), lim);
+            int i0, i1;
+            bool in_cube = true;
+            if constexpr (COLS) {
+                // (every column of the rectangle lies in the cube; the expand pass tests its pixels)
+                const unsigned lim = (unsigned)(f.nleaf - 1);
+                i0 = (int)min((unsigned)(f.col_i0 + R.x), lim);
+                i1 = (int)min((unsigned)(f.col_i1 + R.y), lim);
+            } else {
+                axis_leaf_column(f, ma, R.P0, i0, i1, in_cube);
+            }
             const idx_t m0 = (IDX64 && a0 == 0) ? (idx_t)gmapx64[i0] : (idx_t)gmaps[a0 * f.nleaf + i0];
             const idx_t m1 = (idx_t)gmaps[a1 * f.nleaf + i1];
             // (f.leafcols: occcol holds one mask per leaf column, leaf_columns_kernel)
             if (ESS)
                 R.colmask = occcol[f.leafcols ? ((size_t)ma * f.nleaf + i0) * f.nleaf + i1
                                               : ((size_t)ma * f.ncell + (i0 >> f.cb_shift)) * f.ncell + (i1 >> f.cb_shift)];
-            R.fixed_in = ((int)in_unit(q0) & (int)in_unit(q1) & (int)(m0 >= 0) & (int)(m1 >= 0)) != 0;
+            R.fixed_in = ((int)in_cube & (int)(m0 >= 0) & (int)(m1 >= 0)) != 0;
             R.fixed_off = m0 + m1;
             if (!R.fixed_in && f.zero_transparent) R.s_end = 0;   // the whole ray is TF(0)
             // ESS: a column without an occupied cell holds only alpha-0 samples (exact no-ops of either
@@ -757,7 +813,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
     const bool first = blk == (int)blockIdx.x;
     const int b = first ? b_first : blk;
     if (b < 0 || b >= f.n_work) continue;
-    const WorkTile wt = first ? wt_first : work[b];
+    const WorkTile wt = (first || COLS) ? wt_first : work[b];   // (COLS: one tile per workgroup)
     if (!first) init_ray(wt, R);
     const int x = R.x, y = R.y;
     const bool lane_ok = x < f.W && y < f.H;
@@ -1509,12 +1565,13 @@ size_t vrc_axis1_table_bytes(const VrcFrame& f, int batch) {
     return (n_tab * (f.tsplit ? 8 : 4) + (size_t)f.ncell * 4 + n_tab + 3) & ~(size_t)3;
 }
 
-template <int STATS, int K>
+template <int STATS, int K, bool COLS = false>
 static void launch_vrc_variant(const VrcFrame& f, const WorkTile* work, const int32_t* order, int n_blocks_in,
                                const uint8_t* cls, const int32_t* maps, const int64_t* mapx64, const uint32_t* occ,
                                const float4* tf, int n_tf, float4* out, unsigned long long* stats, hipStream_t st,
                                const float* vol, const int32_t* rawmaps, const unsigned long long* occcol,
-                               const uint8_t* cdist, const int32_t* gtab, int32_t* gtab_out) {
+                               const uint8_t* cdist, const int32_t* gtab, int32_t* gtab_out,
+                               const VrcFrame* colframes = nullptr, int n_frames = 1) {
     const bool f2b = (f.flags & 2) != 0, ess = (f.flags & 1) != 0 && f.zero_transparent;
     const bool shade = (f.flags & 8) != 0;
     const bool idx64 = mapx64 != nullptr, ax1 = f.axis1 >= 0;
@@ -1522,9 +1579,17 @@ static void launch_vrc_variant(const VrcFrame& f, const WorkTile* work, const in
     // f.persist_wgs > 0: persistent grid of 256 CUs x persist_wgs workgroups (multiple of 8)
     int n_blocks = n_blocks_in;
     if (f.persist_wgs > 0) n_blocks = std::min(n_blocks_in, 256 * f.persist_wgs);
+    // the kernel's frame argument: f, or (COLS) the n_frames <= kColBatch frames of the launch, f first
+    typename FrameArg<COLS>::type fa;
+    if constexpr (COLS) {
+        std::memset(&fa, 0, sizeof fa);
+        for (int i = 0; i < n_frames; ++i) fa.f[i] = colframes[i];
+    } else {
+        fa = f;
+    }
 #define VR_L(F2B_, ESS_, I64_, AX_, SH_)                                                                    \
-    hipLaunchKernelGGL((vrc_march_kernel<F2B_, ESS_, I64_, AX_, K, SH_, STATS>), dim3(n_blocks), dim3(kWgThreads), \
-                       lds, st, f, work, order, cls, maps, mapx64, occ, tf, n_tf, out, stats, vol, rawmaps, occcol, cdist, gtab, gtab_out)
+    hipLaunchKernelGGL((vrc_march_kernel<F2B_, ESS_, I64_, AX_, K, SH_, STATS, COLS>), dim3(n_blocks, n_frames), dim3(kWgThreads), \
+                       lds, st, fa, work, order, cls, maps, mapx64, occ, tf, n_tf, out, stats, vol, rawmaps, occcol, cdist, gtab, gtab_out)
 #define VR_L2(I64_, AX_, SH_)                                                                            \
     if (f2b) { if (ess) VR_L(true, true, I64_, AX_, SH_); else VR_L(true, false, I64_, AX_, SH_); } \
     else { if (ess) VR_L(false, true, I64_, AX_, SH_); else VR_L(false, false, I64_, AX_, SH_); }
@@ -1532,7 +1597,12 @@ static void launch_vrc_variant(const VrcFrame& f, const WorkTile* work, const in
                              : (ax1 ? (f.zrun && !shade ? kGeomAxis1Run
                                                         : (f.tsplit && !shade && !idx64 ? kGeomAxis1Z : kGeomAxis1))
                                     : kGeomOrtho);
-    if (shade) {
+    if constexpr (COLS) {
+        // the column march: axis-aligned views of 32-bit volumes without shading (host gate)
+        if (geom == kGeomAxis1) { VR_L2(false, kGeomAxis1, false) }
+        else if (geom == kGeomAxis1Run) { VR_L2(false, kGeomAxis1Run, false) }
+        else if (geom == kGeomAxis1Z) { VR_L2(false, kGeomAxis1Z, false) }
+    } else if (shade) {
         if (geom == kGeomConic) { if (idx64) { VR_L2(true, kGeomConic, true) } else { VR_L2(false, kGeomConic, true) } }
         else if (geom == kGeomAxis1) { if (idx64) { VR_L2(true, kGeomAxis1, true) } else { VR_L2(false, kGeomAxis1, true) } }
         else if (idx64) { VR_L2(true, kGeomOrtho, true) } else { VR_L2(false, kGeomOrtho, true) }
@@ -1956,6 +2026,78 @@ hipError_t launch_vrc_march(const VrcFrame& f, const WorkTile* work, const int32
     else
         launch_vrc_variant<0, 8>(f, work, order, n_blocks, cls, maps, mapx64, occ, tf, n_tf, out, nullptr, st,
                                  vol, rawmaps, occcol, cdist, gtab, gtab_out);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Column path of axis-aligned views (vr_options.axis_columns).  Every ray of such a view stays in
+// one leaf column, and its march is a function of that column and the frame-wide sample table
+// alone, so all the pixels over a column get the same float4 bit for bit.  The column march
+// (vrc_march_kernel, COLS) marches each column of the visible leaf rectangle once into the column
+// buffer; this pass copies a pixel's column to the frame -- the 8 x 8-rays-per-wave mapping, work
+// list and background-only workgroups of the per-pixel march, its non-temporal float4 stores.  A
+// pixel outside the unit cube (or the rectangle: a culled tile's, by the host's bound) is the
+// background, exactly what the per-pixel march stores for a ray that is TF(0) throughout.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void axis_expand_kernel(VrcFrame f, const WorkTile* __restrict__ work,
+                                                          const float4* __restrict__ colbuf,
+                                                          float4* __restrict__ out) {
+    const float4 bg = make_float4(f.bg[0], f.bg[1], f.bg[2], 1.0f);
+    if ((int)blockIdx.x >= f.bg_first) {
+        const int e0 = f.bg_first + ((int)blockIdx.x - f.bg_first) * f.bg_group;
+        for (int i = 0; i < f.bg_group; ++i) {
+            const int e = e0 + i;
+            if (e >= f.n_work) break;
+            int x, y;
+            ray_of_thread(work[e], x, y);
+            if (x < f.W && y < f.H) store_f4(out + (int64_t)x * f.H + y, bg);
+        }
+        return;
+    }
+    if ((int)blockIdx.x >= f.n_work) return;
+    const WorkTile wt = work[blockIdx.x];
+    int x, y;
+    ray_of_thread(wt, x, y);
+    if (!(x < f.W && y < f.H)) return;   // (a hole of the dealt list lies far off the frame)
+    float4 v = bg;
+    if (wt.slot >= 0) {
+        float P0[3];
+        int i0, i1;
+        bool in_cube;
+        ray_origin(f, x, y, P0);
+        axis_leaf_column(f, f.axis1, P0, i0, i1, in_cube);
+        const unsigned c0 = (unsigned)(i0 - f.col_i0), c1 = (unsigned)(i1 - f.col_i1);
+        if (in_cube && c0 < (unsigned)f.col_n0 && c1 < (unsigned)f.col_n1) v = colbuf[c0 * (unsigned)f.col_n1 + c1];
+    }
+    store_f4(out + (int64_t)x * f.H + y, v);
+}
+
+hipError_t launch_axis_expand(const VrcFrame& f, const WorkTile* work, int n_blocks, const float4* colbuf, float4* out,
+                              hipStream_t st) {
+    if (n_blocks <= 0) return hipSuccess;
+    hipLaunchKernelGGL(axis_expand_kernel, dim3(n_blocks), dim3(kWgThreads), 0, st, f, work, colbuf, out);
+    return hipGetLastError();
+}
+
+// The column march of frame f (f.W x f.H = the leaf-column rectangle col_n0 x col_n1, f.n_work its
+// 16 x 16 tiles) into colbuf[col_ofs + (i0 - col_i0) * col_n1 + (i1 - col_i1)]: the marches of the
+// n_frames <= kColBatch frames fs[] in one launch (grid y).  All take the first one's kernel variant
+// and LDS size (host: same params, view axis, table form), and n_blocks = their common n_slots covers
+// the largest rectangle.
+hipError_t launch_vrc_columns(const VrcFrame* fs, int n_frames, int n_blocks, const uint8_t* cls, const int32_t* maps,
+                              const float4* tf, int n_tf, float4* colbuf, hipStream_t st, int batch,
+                              const unsigned long long* occcol, const int32_t* gtab, int32_t* gtab_out) {
+    if (n_frames < 1 || n_frames > kColBatch) return hipErrorInvalidValue;
+    const VrcFrame& f = fs[0];
+    const VrcFrame* colframes = fs;
+    if (vrc_batch(f, batch) == 16)
+        launch_vrc_variant<0, 16, true>(f, nullptr, nullptr, n_blocks, cls, maps, nullptr, nullptr, tf, n_tf, colbuf,
+                                        nullptr, st, nullptr, nullptr, occcol, nullptr, gtab, gtab_out, colframes,
+                                        n_frames);
+    else
+        launch_vrc_variant<0, 8, true>(f, nullptr, nullptr, n_blocks, cls, maps, nullptr, nullptr, tf, n_tf, colbuf,
+                                       nullptr, st, nullptr, nullptr, occcol, nullptr, gtab, gtab_out, colframes,
+                                       n_frames);
     return hipGetLastError();
 }
 

@@ -94,6 +94,30 @@ __device__ __forceinline__ bool in_unit(float q) {
     return __float_as_uint(q) < 0x3f800000u;
 }
 
+// The screen point of pixel (x, y) (kernel.cu:55-59): tlc + x*rsw/W*right + y*rsh/H*(-up), left to
+// right -- the origin of its orthographic ray.
+__device__ __forceinline__ void ray_origin(const VrcFrame& f, int x, int y, float P0[3]) {
+    const float A = (float)x * f.rsw / (float)f.W;
+    const float B = (float)y * f.rsh / (float)f.H;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) P0[c] = (f.tlc[c] + A * f.right[c]) + B * (-f.up[c]);
+}
+
+// Axis-aligned views along axis ma: the leaf column of the ray from P0 -- its leaf indices on the two
+// fixed axes a0 < a1 (q_c = P0_c + 0.5 exactly, since front_c == 0), clamped so lookups with them
+// are unconditional -- and whether the ray lies inside the unit cube on both.  The per-pixel march
+// (init_ray) and the column path's expand pass (axis_expand_kernel) both take a pixel's column from
+// here, so the two cannot drift apart.
+__device__ __forceinline__ void axis_leaf_column(const VrcFrame& f, int ma, const float P0[3], int& i0, int& i1,
+                                                 bool& in_cube) {
+    const float q0 = (ma == 0 ? P0[1] : P0[0]) + 0.5f;
+    const float q1 = (ma == 2 ? P0[1] : P0[2]) + 0.5f;
+    const unsigned lim = (unsigned)(f.nleaf - 1);
+    i0 = (int)min((unsigned)(int)(q0 * f.leaves), lim);
+    i1 = (int)min((unsigned)(int)(q1 * f.leaves), lim);
+    in_cube = ((int)in_unit(q0) & (int)in_unit(q1)) != 0;
+}
+
 // Counting passes (vr_count_work, never a timed launch): a lane's class gathers that touched memory,
 // the bytes they read and the samples it evaluated, summed over the frame into stats[0], [2], [1]
 __device__ __forceinline__ void count_work(unsigned long long* stats, unsigned gathers, unsigned bytes,

@@ -41,6 +41,7 @@ EXPORTED = [
     "vr_assemble_tile_slots_multi", "vr_options_default", "vr_create_ex", "vr_get_options", "vr_set_options",
     "vr_create_multi", "vr_comm_unique_id", "vr_create_rank", "vr_group_info", "vr_group_tiles", "vr_render_png",
     "vr_render_batch", "vr_create_multi_ex", "vr_group_timing_read", "vr_count_work", "vr_group_traffic_read",
+    "vr_axis_columns_plan",
 ]
 VR_COMM_ID_BYTES = 128
 VR_TRANSPORT_NONE, VR_TRANSPORT_RCCL, VR_TRANSPORT_PEER_COPY = 0, 1, 2
@@ -109,7 +110,8 @@ class Options(C.Structure):
                 ("run_words", C.c_int32),
                 ("table_split", C.c_int32),
                 ("test_corners", C.c_int32),
-                ("leaf_columns", C.c_int32)]
+                ("leaf_columns", C.c_int32),
+                ("axis_columns", C.c_int32)]
 
 
 class WorkCount(C.Structure):
@@ -172,6 +174,7 @@ def lib():
         "vr_count_samples": ([vp, P(RenderParams), P(Camera), P(C.c_uint64)], C.c_int),
         "vr_count_marched": ([vp, P(RenderParams), P(Camera), P(C.c_uint64), P(C.c_uint64)], C.c_int),
         "vr_count_work": ([vp, P(RenderParams), P(Camera), P(WorkCount)], C.c_int),
+        "vr_axis_columns_plan": ([vp, P(RenderParams), P(Camera), P(C.c_int32)], C.c_int),
         "vr_synchronize": ([vp], C.c_int),
         "vr_set_stream": ([vp, vp], C.c_int),
         "vr_params_default": ([C.c_int32, C.c_int32, C.c_int32, P(RenderParams)], C.c_int),
@@ -553,6 +556,14 @@ class VolumeRenderer:
         w = WorkCount()
         _check(lib().vr_count_work(self._ctx, C.byref(params), C.byref(camera), C.byref(w)), "vr_count_work")
         return {"gathers": int(w.gathers), "bytes": int(w.bytes), "samples": int(w.samples)}
+
+    def axis_columns_plan(self, params, camera) -> dict:
+        """{columns, n0, n1, pixels}: whether vr_render takes the axis views' column path for this
+        frame (vr_options.axis_columns), the leaf columns of the visible rectangle on the two fixed
+        axes and the rectangle's pixels (vr_axis_columns_plan: decided on the host)."""
+        o = (C.c_int32 * 4)()
+        _check(lib().vr_axis_columns_plan(self._ctx, C.byref(params), C.byref(camera), o), "vr_axis_columns_plan")
+        return {"columns": bool(o[0]), "n0": int(o[1]), "n1": int(o[2]), "pixels": int(o[3])}
 
     def synchronize(self):
         _check(lib().vr_synchronize(self._ctx), "vr_synchronize")
