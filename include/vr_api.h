@@ -51,6 +51,17 @@ extern "C" {
 /* ---- render modes (utils.h:13-18 algorithm IDs) ------------------------------------------- */
 #define VR_MODE_VRC 1      /* octree-leaf nearest sampling (kernel.cu:40-70)                   */
 #define VR_MODE_TEST 5     /* classify-then-trilinear over the raw grid (kernel.cu:72-187)     */
+#define VR_MODE_DVR 6      /* trilinear sample of the scalar field, then TF classification (no reference
+                              mode: ids 0-5 are the reference's).  TEST's sample positions and in-volume
+                              test; corners (int)p and min((int)p + 1, d - 1) per axis (clamp to edge),
+                              weights p - (int)p; the 8 voxel values (a non-finite one reads as 0) lerped
+                              a*(1 - w) + b*w in y, then x, then z, every operation rounded on its own;
+                              the result v classified TF((float)((double)v / cal_max)).  A sample outside
+                              the volume is TF((float)(0.0f / cal_max)).  VR_FLAG_ESS and VR_FLAG_ERT
+                              apply; VR_FLAG_SHADE / VR_FLAG_CONIC are VR_EINVAL; cal_max must be finite
+                              and > 0 (VR_EINVAL at render); the array the march reads (a byte copy of
+                              the volume, else the float volume) must stay below 2^31 bytes (VR_ERANGE).
+                              vr_count_samples / vr_count_marched / vr_count_work: VR_EINVAL            */
 
 /* ---- render flags -------------------------------------------------------------------------- */
 #define VR_FLAG_ESS 1      /* empty-space skipping (bitwise exact: skips only alpha-0 samples)  */
@@ -184,6 +195,11 @@ typedef struct {
                                   the same value bit for bit.  0 = off (one march per pixel), 1 = auto
                                   (default: when the visible rectangle has at least 2 pixels per
                                   column), 2 = whenever the scope allows.  Bitwise the same frames    */
+    /* layout (vr_create_ex only) */
+    int32_t dvr_volume;        /* VR_MODE_DVR frames gather their 8 corner values from: 0 (default) = a byte
+                                  copy of the volume when every voxel is an integer in 0..255 (lossless:
+                                  four dword gathers per sample), else the float volume; 1 = always the
+                                  float volume (eight float gathers).  Bitwise the same frames        */
 } vr_options;
 
 int vr_options_default(vr_options* out);
@@ -451,6 +467,20 @@ int vr_camera_reset(vr_camera* out);
 /* The reference's transfer function (TransferFunction.cu:19-23, Material.cpp:6-67); returns
  * the number of intervals written (4); out must hold >= 4. */
 int vr_default_transfer_function(vr_tf_interval* out, int32_t capacity);
+
+/* The transfer function as segments of the ordered floats, for classifying an interpolated value
+ * without a division (VR_MODE_DVR; no GPU needed).  For cal_max finite and > 0 the map
+ * v -> (float)((double)v / cal_max) is non-decreasing, so the classes of the interval scan (last
+ * closed interval containing the value wins, default interval 0) cut -inf..+inf into at most
+ * 2 n_tf + 1 runs.  Segment j holds the floats starts[j] <= v < starts[j + 1] (the last one up to
+ * +inf), starts[0] = -INFINITY, and classes[j] is the scan's class of (float)((double)v / cal_max)
+ * for every such v; neighbouring segments differ in class.  Each bound is found by bisection over
+ * the floats' bit patterns against that very expression, so comparing v with the starts IS the
+ * literal formula, bit for bit.  Writes up to `capacity` segments (starts / classes may be NULL
+ * with capacity 0) and their number into *n_out; VR_ERANGE when capacity is too small, VR_EINVAL
+ * for a bad TF or cal_max. */
+int vr_tf_segments(const vr_tf_interval* tf, int32_t n_tf, double cal_max, float* starts, int32_t* classes,
+                   int32_t capacity, int32_t* n_out);
 
 /* NiftiFile loader on its own (no GPU): fills dims[3] and *cal_max; if voxels != NULL also copies
  * dims[0]*dims[1]*dims[2] float32 values (x-major) into it.  Same hardening as

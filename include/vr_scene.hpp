@@ -96,6 +96,14 @@ public:
     const Material::Material* getMaterial(float value) const {
         return &material_intervals[getMaterialIndex(value)].material;
     }
+    // The classes of (float)((double)v / cal_max) over the ordered floats v (cal_max finite, > 0): runs
+    // [start, next start) of one class each, the first from -infinity, neighbours of different class;
+    // each bound bisected over the floats' bit patterns against that expression (vr_tf_segments).
+    struct Segment {
+        float start;
+        int material_index;
+    };
+    std::vector<Segment> segments(double cal_max) const;
     std::vector<MatInterval> material_intervals;
     int size() const { return (int)material_intervals.size(); }
 };

@@ -190,6 +190,15 @@ struct vr_ctx {
     // (cleared when the classes change)
     mutable std::map<std::vector<uint32_t>, std::vector<int32_t>> vis_cache;
     bool cls_test_valid = false;
+    // VR_MODE_DVR (vr_dvr.hip), built on the first DVR frame: the byte copy of the volume (dvr_u8_state
+    // 0 = not tried, 1 = built and lossless, 2 = the volume is not bytes / the option forbids it), the
+    // min/max of the cells (2^dvr_tcb voxels per axis), and -- rebuilt when the TF changes (dvr_tf_valid)
+    // -- the TF's segments (starts, colours) and the cells' occupancy bits
+    vr::DevBuf dvr_u8, dvr_minmax, dvr_occ, dvr_start, dvr_seg;
+    int dvr_u8_state = 0;
+    bool dvr_cells_valid = false, dvr_tf_valid = false;
+    int dvr_tcb = 3, dvr_tnc[3] = {0, 0, 0};
+    vr::DvrFrame dvr_frame{};                // nseg, seg0 and the SGPR starts of the current TF
     // TEST: a voxel on the volume's faces is not class 0 (test_faces_kernel; 1 until classified)
     vr::DevBuf faces_flag;
     int32_t test_faces_dirty = 1;

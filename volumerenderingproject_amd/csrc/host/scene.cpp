@@ -1,9 +1,11 @@
 // scene.cpp -- host model of the render path (see scene.h for the reference map).
 #include "scene.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <fstream>
+#include <limits>
 
 #include "../../../include/vr_api.h"
 
@@ -175,6 +177,55 @@ int TransferFunction::getMaterialIndex(float value) const {
     for (int i = 0; i < size(); ++i)
         if (value >= material_intervals[i].lower_bound && value <= material_intervals[i].higher_bound) r = i;
     return r;
+}
+
+// Floats in their numeric order as unsigned keys (negative: all bits flipped; positive: sign bit
+// set): -inf = 0x007fffff, -0 = 0x7fffffff, +0 = 0x80000000, +inf = 0xff800000; NaNs lie outside.
+static uint32_t float_key(float v) {
+    uint32_t b;
+    std::memcpy(&b, &v, 4);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+static float key_float(uint32_t k) {
+    const uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    float v;
+    std::memcpy(&v, &b, 4);
+    return v;
+}
+
+std::vector<TransferFunction::Segment> TransferFunction::segments(double cal_max) const {
+    if (!(cal_max > 0.0) || !std::isfinite(cal_max)) throw Error(VR_EINVAL, "segments: cal_max must be finite and > 0");
+    const uint32_t k_lo = float_key(-std::numeric_limits<float>::infinity());
+    const uint32_t k_end = float_key(std::numeric_limits<float>::infinity()) + 1u;
+    // the literal expression (getColorFromNF's v / cal_max in double, rounded to float)
+    auto norm = [cal_max](uint32_t k) { return (float)((double)key_float(k) / cal_max); };
+    // first key in [k_lo, k_end] whose normalised value passes `pred` (monotone: false ... true);
+    // k_end = none.  32 halvings cover any range of 32-bit keys.
+    auto first_true = [&](auto pred) {
+        uint32_t lo = k_lo, hi = k_end;
+        for (int step = 0; step < 32; ++step) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (pred(norm(mid))) hi = mid; else lo = mid + (lo < hi ? 1u : 0u);
+        }
+        return hi;
+    };
+    std::vector<uint32_t> cuts = {k_lo};
+    for (const MatInterval& m : material_intervals) {
+        const float lb = m.lower_bound, hb = m.higher_bound;
+        cuts.push_back(first_true([lb](float n) { return n >= lb; }));
+        // (first value past the closed interval's end: !(n <= hb) would also pass NaN bounds, which
+        // contain nothing and cut nothing)
+        cuts.push_back(first_true([hb](float n) { return n > hb; }));
+    }
+    std::sort(cuts.begin(), cuts.end());
+    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+    std::vector<Segment> out;
+    for (uint32_t k : cuts) {
+        if (k >= k_end) break;
+        const int cls = getMaterialIndex(norm(k));   // constant up to the next cut
+        if (out.empty() || out.back().material_index != cls) out.push_back({key_float(k), cls});
+    }
+    return out;
 }
 
 // ============================================ OctreeHandler ==================================

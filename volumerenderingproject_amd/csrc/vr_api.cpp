@@ -5,6 +5,7 @@
 //   vol        float32 volume, x-major (kept for re-classification when the TF changes)
 //   cls_vrc    uint8 class per voxel for VRC      (TF of max(0,v)/(float)(int)cal_max)
 //   cls_test   uint8 class per voxel for TEST     (TF of (float)(v/cal_max)), built on first use
+//   dvr_*      VR_MODE_DVR: byte copy of the volume, cell min/max and bits, TF segments, built on first use
 //   maps       3 x 2^D int32 leaf -> voxel maps (the octree leaf grid in closed form)
 //   occ        macro-cell occupancy bitmask over the leaf grid (ESS)
 //   tf_rgba    class colours; tf_lohi interval bounds
@@ -62,6 +63,12 @@ hipError_t launch_test_march(const TestFrame&, const WorkTile*, const int32_t*, 
                              const int32_t*, unsigned long long*, const int32_t*, int);
 hipError_t launch_test_occupancy(const uint8_t*, int64_t, int64_t, int64_t, int, int, int, int, const uint8_t*,
                                  unsigned long long*, hipStream_t);
+hipError_t launch_dvr_march(const TestFrame&, const DvrFrame&, const WorkTile*, int, const void*, bool, const float*,
+                            const float4*, const uint32_t*, float4*, hipStream_t);
+size_t dvr_lds_bytes(const TestFrame&, const DvrFrame&, bool);
+hipError_t launch_dvr_bytes(const float*, int64_t, uint8_t*, int32_t*, hipStream_t);
+hipError_t launch_dvr_minmax(const float*, int64_t, int64_t, int64_t, int, int, int, int, float2*, hipStream_t);
+hipError_t launch_dvr_cells(const float2*, int64_t, const float*, const float4*, int, unsigned long long*, hipStream_t);
 hipError_t launch_assemble(int, int, int, int, int, int, const float4*, float4*, int, hipStream_t);
 hipError_t launch_assemble_list(int, int, int, int, const int32_t*, const float4*, float4, float4*, int, hipStream_t,
                                 int n_frames = 1);
@@ -87,6 +94,17 @@ int tf_index(const std::vector<vr_tf_interval>& tf, float v) {
     for (int i = 0; i < (int)tf.size(); ++i)
         if (v >= tf[i].lo && v <= tf[i].hi) r = i;
     return r;
+}
+
+// TransferFunction::segments for the C-ABI's intervals (vr_tf_segments; the DVR march's tables)
+std::vector<TransferFunction::Segment> tf_segments(const vr_tf_interval* tf, int n_tf, double cal_max) {
+    std::vector<MatInterval> iv((size_t)n_tf);
+    for (int i = 0; i < n_tf; ++i) {
+        iv[i].material = Material::Material{"", {tf[i].rgba[0], tf[i].rgba[1], tf[i].rgba[2], tf[i].rgba[3]}, 0.0};
+        iv[i].lower_bound = tf[i].lo;
+        iv[i].higher_bound = tf[i].hi;
+    }
+    return TransferFunction(std::move(iv)).segments(cal_max);
 }
 
 void set_device(vr_ctx* c) { hip_check(hipSetDevice(c->device)); }
@@ -287,6 +305,7 @@ void build_layout(vr_ctx* c, int cbits) {
 // (Re)classify the volume and rebuild the occupancy pyramid for the current TF.
 void classify(vr_ctx* c, bool need_test) {
     const int n_tf = (int)c->tf.size();
+    c->dvr_tf_valid = false;   // (the DVR march's segment tables and cell bits follow the TF: ensure_dvr)
     std::vector<float> lohi(2 * n_tf);
     std::vector<float4> rgba(n_tf);
     std::vector<uint8_t> anz(kMaxTf, 0);
@@ -532,6 +551,7 @@ void check_options(const vr_options& o) {
     if (o.test_corners < 0 || o.test_corners > 3) throw Error(VR_EINVAL, "vr_options: test_corners must be 0..3");
     if (o.leaf_columns < 0 || o.leaf_columns > 1) throw Error(VR_EINVAL, "vr_options: leaf_columns must be 0 or 1");
     if (o.axis_columns < 0 || o.axis_columns > 2) throw Error(VR_EINVAL, "vr_options: axis_columns must be 0, 1 or 2");
+    if (o.dvr_volume < 0 || o.dvr_volume > 1) throw Error(VR_EINVAL, "vr_options: dvr_volume must be 0 or 1");
     if (o.farm_tile <= 0 || o.farm_tile % kWgRaysX || o.farm_tile > 4096)
         throw Error(VR_EINVAL, "vr_options: farm_tile must be a positive multiple of 16");
     if (!(o.farm_rank0_weight > 0.0f && o.farm_rank0_weight <= 1e9f))
@@ -775,7 +795,9 @@ WorkCache* frame_list(vr_ctx* c, const vr_params* p, const vr_camera* cam, const
 #ifndef VR_TEST_AXIS_COLUMN_DEAL
 #define VR_TEST_AXIS_COLUMN_DEAL 0
 #endif
-    const int deal = (p->mode == VR_MODE_TEST && (VR_TEST_AXIS_COLUMN_DEAL || make_test(c, p, cam).axt < 0)) ? 1 : 0;
+    // (DVR frames: one general march for every view, its volume read like the corner volume)
+    const int deal = (p->mode == VR_MODE_DVR ||
+                      (p->mode == VR_MODE_TEST && (VR_TEST_AXIS_COLUMN_DEAL || make_test(c, p, cam).axt < 0))) ? 1 : 0;
     std::vector<uint32_t> key = {(uint32_t)W, (uint32_t)H, (uint32_t)tx0, (uint32_t)tx1, (uint32_t)ty0, (uint32_t)ty1,
                                  (uint32_t)ma, (uint32_t)deal};
     if (ma >= 0) {
@@ -830,7 +852,8 @@ int hull_edges(const vr_ctx* c, const vr_params* p, const vr_camera* cam, float 
 // nothing can be visible, 2 when no claim can be made (TEST mode, opaque TF(0), a corner behind a
 // conic camera, a NaN camera), 1 with the points in xy.
 int project_box(const vr_ctx* c, const vr_params* p, const vr_camera* cam, double xy[8][2]) {
-    if (p->mode == VR_MODE_TEST) return project_box_test(c, p, cam, xy);
+    // (DVR: TEST's positions and in-volume test, TF(0) outside)
+    if (p->mode == VR_MODE_TEST || p->mode == VR_MODE_DVR) return project_box_test(c, p, cam, xy);
     if (p->mode != VR_MODE_VRC || !c->zero_transparent) return 2;
     double lo[3], hi[3];
     for (int a = 0; a < 3; ++a) {
@@ -1124,7 +1147,8 @@ std::vector<int32_t> visible_tiles_uncached(const vr_ctx* c, const vr_params* p,
 void check_params(const vr_params* p) {
     if (!p || p->width <= 0 || p->height <= 0 || p->samples_per_ray <= 0 || p->width > 65535 || p->height > 65535)
         throw Error(VR_EINVAL, "vr_params: bad width/height/samples_per_ray");
-    if (p->mode != VR_MODE_VRC && p->mode != VR_MODE_TEST) throw Error(VR_EINVAL, "vr_params: unknown mode");
+    if (p->mode != VR_MODE_VRC && p->mode != VR_MODE_TEST && p->mode != VR_MODE_DVR)
+        throw Error(VR_EINVAL, "vr_params: unknown mode");
     if (p->flags & ~(VR_FLAG_ESS | VR_FLAG_ERT | VR_FLAG_SHADE | VR_FLAG_CONIC))
         throw Error(VR_EINVAL, "vr_params: unknown flags");
     if ((p->flags & (VR_FLAG_SHADE | VR_FLAG_CONIC)) && p->mode != VR_MODE_VRC)
@@ -1499,6 +1523,79 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, WorkCache
     launch_frame(c, p, cam, wv, out, out_tiles, tile_w, tile_h, out_rgb, rect, pre);
 }
 
+// VR_MODE_DVR's lazy state, on c->stream: the byte copy of the volume (first frame; kept only when
+// lossless), the cells' min/max (first frame) and -- whenever the TF changed -- the TF's segments and
+// the cells' occupancy bits.  Throws VR_EINVAL for a cal_max the mode is not defined for and
+// VR_ERANGE for a volume past 32-bit byte offsets.
+void ensure_dvr(vr_ctx* c) {
+    if (!(c->cal_max > 0.0) || !std::isfinite(c->cal_max))
+        throw Error(VR_EINVAL, "VR_MODE_DVR: cal_max must be finite and > 0");
+    const int64_t n = c->d[0] * c->d[1] * c->d[2];
+    const int64_t lim = ((int64_t)1 << 31) - 1;
+    if (c->dvr_u8_state == 0) {
+        c->dvr_u8_state = 2;
+        if (c->opt.dvr_volume == 0 && n + kDvrPad <= lim) {
+            DevBuf flag;
+            flag.ensure(sizeof(int32_t));
+            c->dvr_u8.ensure((size_t)n + kDvrPad);
+            hip_check(hipMemsetAsync(c->dvr_u8.as<uint8_t>() + n, 0, kDvrPad, c->stream));
+            hip_check(hipMemsetAsync(flag.p, 0, sizeof(int32_t), c->stream));
+            hip_check(launch_dvr_bytes(c->vol.as<float>(), n, c->dvr_u8.as<uint8_t>(), flag.as<int32_t>(), c->stream));
+            int32_t lossy = 1;
+            hip_check(hipMemcpyAsync(&lossy, flag.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            ctx_sync(c, c->stream);
+            if (lossy == 0) c->dvr_u8_state = 1;
+            else c->dvr_u8.reset();
+        }
+    }
+    if (c->dvr_u8_state != 1 && n * 4 > lim) throw Error(VR_ERANGE, "VR_MODE_DVR: volume too large for 32-bit offsets");
+    if (!c->dvr_cells_valid) {   // cells of 8^3 voxels, coarser until the bitmask is <= 2^18 bits
+        c->dvr_tcb = 3;
+        auto nc = [&](int a) { return (int)((c->d[a] + (1 << c->dvr_tcb) - 1) >> c->dvr_tcb); };
+        while ((int64_t)nc(0) * nc(1) * nc(2) > (1 << 18)) ++c->dvr_tcb;
+        for (int a = 0; a < 3; ++a) c->dvr_tnc[a] = nc(a);
+        const int64_t cells = (int64_t)c->dvr_tnc[0] * c->dvr_tnc[1] * c->dvr_tnc[2];
+        c->dvr_minmax.ensure((size_t)cells * sizeof(float2));
+        c->dvr_occ.ensure((size_t)((cells + 63) / 64) * 8);
+        hip_check(launch_dvr_minmax(c->vol.as<float>(), c->d[0], c->d[1], c->d[2], c->dvr_tcb, c->dvr_tnc[0],
+                                    c->dvr_tnc[1], c->dvr_tnc[2], c->dvr_minmax.as<float2>(), c->stream));
+        group_mark(c);
+        c->dvr_cells_valid = true;
+        c->dvr_tf_valid = false;
+    }
+    if (!c->dvr_tf_valid) {
+        const std::vector<TransferFunction::Segment> seg = tf_segments(c->tf.data(), (int)c->tf.size(), c->cal_max);
+        const int nseg = (int)seg.size();
+        std::vector<float> starts((size_t)nseg);
+        std::vector<float4> rgba((size_t)nseg);
+        DvrFrame g;
+        std::memset(&g, 0, sizeof g);
+        g.nseg = nseg;
+        for (int j = 0; j < kDvrSeg8; ++j) g.start[j] = std::numeric_limits<float>::quiet_NaN();
+        for (int j = 0; j < nseg; ++j) {
+            const vr_tf_interval& t = c->tf[(size_t)seg[j].material_index];
+            starts[j] = seg[j].start;
+            rgba[j] = make_float4(t.rgba[0], t.rgba[1], t.rgba[2], t.rgba[3]);
+            if (j >= 1 && seg[j].start <= 0.0f) g.seg0 = j;   // the segment of the value 0 (outside the volume)
+            if (j >= 1 && j <= kDvrSeg8 && nseg <= 1 + kDvrSeg8) g.start[j - 1] = seg[j].start;
+        }
+        ctx_sync(c, c->stream);   // (queued launches read the old tables)
+        c->dvr_start.ensure((size_t)kMaxDvrSeg * sizeof(float));
+        c->dvr_seg.ensure((size_t)kMaxDvrSeg * sizeof(float4));
+        hip_check(hipMemcpyAsync(c->dvr_start.p, starts.data(), starts.size() * sizeof(float), hipMemcpyHostToDevice,
+                                 c->stream));
+        hip_check(hipMemcpyAsync(c->dvr_seg.p, rgba.data(), rgba.size() * sizeof(float4), hipMemcpyHostToDevice,
+                                 c->stream));
+        const int64_t cells = (int64_t)c->dvr_tnc[0] * c->dvr_tnc[1] * c->dvr_tnc[2];
+        hip_check(launch_dvr_cells(c->dvr_minmax.as<float2>(), cells, c->dvr_start.as<float>(), c->dvr_seg.as<float4>(),
+                                   nseg, c->dvr_occ.as<unsigned long long>(), c->stream));
+        group_mark(c);
+        ctx_sync(c, c->stream);   // (starts and rgba are host temporaries)
+        c->dvr_frame = g;
+        c->dvr_tf_valid = true;
+    }
+}
+
 void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const WorkView& wv, float4* out, int out_tiles,
                   int tile_w, int tile_h, int out_rgb, const TileRect* rect, const ColumnSlice* pre) {
     const WorkView* wc = &wv;
@@ -1641,7 +1738,9 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
                                    c->cdist_p, gtab, gtab_out, c->count_ptr));
         if (gtab_out) c->axtab[c->stream].key = std::move(pub_key);   // valid for later launches on this stream
     } else {
-        if (!c->cls_test_valid) classify(c, true);
+        const bool dvr = p->mode == VR_MODE_DVR;
+        if (dvr) ensure_dvr(c);
+        else if (!c->cls_test_valid) classify(c, true);
         TestFrame f = make_test(c, p, cam);
         f.out_tiles = out_tiles; f.tile_w = tile_w; f.tile_h = tile_h; f.n_work = wc->n_work; f.out_rgb = out_rgb;
         // whole frames: the work tiles off the dataset box's projection (project_box_test) are stored
@@ -1654,6 +1753,25 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             f.bg_group = kBgGroup;
             n_launch = wc->bg_first + (wc->n_work - wc->bg_first + kBgGroup - 1) / kBgGroup;
         }
+        if (dvr) {
+            // the DVR march: TEST's frame with its own cells, plus the TF's segments (ensure_dvr)
+            const int64_t n = c->d[0] * c->d[1] * c->d[2];
+            const bool u8 = c->dvr_u8_state == 1;
+            f.axt = -1;
+            f.tcb = c->dvr_tcb;
+            for (int a = 0; a < 3; ++a) f.tnc[a] = c->dvr_tnc[a];
+            f.occ_words = (int)(((int64_t)f.tnc[0] * f.tnc[1] * f.tnc[2] + 31) / 32);
+            f.occ_lds = (f.occ_words <= 8192 && c->occ_lds) ? 1 : 0;
+            DvrFrame g = c->dvr_frame;
+            g.vol_bytes = (int32_t)(u8 ? n + 16 : n * 4);   // (the byte copy: a dword at the last voxel stays inside)
+            // LDS budget: the B table first (its entries are then computed per sample, the same
+            // expressions), then the cell bits (read through the cache instead)
+            const bool ess = (f.flags & VR_FLAG_ESS) && f.zero_transparent;
+            if (dvr_lds_bytes(f, g, ess) > (size_t)kDvrLdsMax) f.sep_tab = 0;
+            if (dvr_lds_bytes(f, g, ess) > (size_t)kDvrLdsMax) f.occ_lds = 0;
+            hip_check(launch_dvr_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8, c->dvr_start.as<float>(),
+                                       c->dvr_seg.as<float4>(), c->dvr_occ.as<uint32_t>(), out, c->stream));
+        } else {
         // axis views: the march axis's tables built here once per view and staged by every workgroup
         // (per stream, like the VRC view tables; a new view first drains the launches of this stream)
         const int32_t* ztab = nullptr;
@@ -1691,6 +1809,7 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
                                     c->tcc.p ? c->tcc.as<uint8_t>() : nullptr,
                                     c->tcc_lay.p ? c->tcc_lay.as<int32_t>() : nullptr, c->count_ptr, ztab,
                                     ztab_words));
+        }
     }
     if (c->timing) {
         hip_check(hipEventRecord(ev.second, c->stream));
@@ -1791,7 +1910,8 @@ void destroy_ctx_single(vr_ctx* c) {
     if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
     for (DevBuf* b : {&c->vol, &c->cls_vrc, &c->cls8, &c->cls_gen, &c->layout_gen, &c->pmaps_gen, &c->pmaps_pad, &c->pmaps_gen_pad, &c->cls_test, &c->maps, &c->pmaps, &c->pmapx64, &c->occ, &c->tf_rgba,
                       &c->tf_lohi, &c->alpha_nz, &c->frame, &c->counter, &c->layout, &c->egress, &c->occ_test,
-                      &c->occ_cols, &c->occ_leafcols, &c->cdist, &c->nrm, &c->tcol, &c->tcc, &c->tcc_lay, &c->faces_flag})
+                      &c->occ_cols, &c->occ_leafcols, &c->cdist, &c->nrm, &c->tcol, &c->tcc, &c->tcc_lay, &c->faces_flag,
+                      &c->dvr_u8, &c->dvr_minmax, &c->dvr_occ, &c->dvr_start, &c->dvr_seg})
         b->reset();
     c->work_cache.clear();
     c->slot_maps.clear();
@@ -1913,6 +2033,7 @@ int vr_options_default(vr_options* o) {
     o->test_corners = 0;
     o->leaf_columns = 1;   // C3 default view
     o->axis_columns = 1;
+    o->dvr_volume = 0;
     return VR_OK;
 }
 
@@ -1939,9 +2060,10 @@ int vr_set_options(vr_ctx* c, const vr_options* o) {
         const vr_options& cur = c->opt;
         if (o->brick[0] != cur.brick[0] || o->brick[1] != cur.brick[1] || o->brick[2] != cur.brick[2] ||
             o->cell_shift != cur.cell_shift || o->force_idx64 != cur.force_idx64 || o->class_bits != cur.class_bits ||
-            o->test_corners != cur.test_corners || o->leaf_columns != cur.leaf_columns)
+            o->test_corners != cur.test_corners || o->leaf_columns != cur.leaf_columns ||
+            o->dvr_volume != cur.dvr_volume)
             throw Error(VR_EINVAL,
-                        "vr_set_options: brick / cell_shift / force_idx64 / class_bits / test_corners / leaf_columns are fixed at vr_create_ex");
+                        "vr_set_options: brick / cell_shift / force_idx64 / class_bits / test_corners / leaf_columns / dvr_volume are fixed at vr_create_ex");
         group_for_each(c, [](vr_ctx* pc, void* a) { apply_render_options(pc, *static_cast<const vr_options*>(a)); },
                        const_cast<vr_options*>(o));
         group_options_changed(c);
@@ -2258,6 +2380,7 @@ int vr_assemble_tiles(vr_ctx* c, int32_t W, int32_t H, int32_t tile_w, int32_t t
 
 int vr_count_samples(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64_t* n_in) {
     if (!c || !cam || !n_in) return VR_EINVAL;
+    if (p && p->mode == VR_MODE_DVR) return VR_EINVAL;   // (the counting passes cover VRC and TEST)
     return guard([&] {
         check_params(p);
         set_device(c);
@@ -2281,6 +2404,7 @@ int vr_count_samples(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64
 // axis_columns_plan's scope), and the tests that pin these counts pin that definition.
 int vr_count_work(vr_ctx* c, const vr_params* p, const vr_camera* cam, vr_work_count* out) {
     if (!c || !cam || !out) return VR_EINVAL;
+    if (p && p->mode == VR_MODE_DVR) return VR_EINVAL;   // (no counting instantiation of the DVR march)
     return guard([&] {
         check_params(p);
         set_device(c);
@@ -2526,6 +2650,22 @@ int vr_default_transfer_function(vr_tf_interval* out, int32_t capacity) {
     return t.size();
 }
 
+int vr_tf_segments(const vr_tf_interval* tf, int32_t n_tf, double cal_max, float* starts, int32_t* classes,
+                   int32_t capacity, int32_t* n_out) {
+    if (!tf || n_tf <= 0 || n_tf > kMaxTf || !n_out || capacity < 0) return VR_EINVAL;
+    if (capacity > 0 && (!starts || !classes)) return VR_EINVAL;
+    return guard([&] {
+        const std::vector<TransferFunction::Segment> seg = tf_segments(tf, n_tf, cal_max);
+        *n_out = (int32_t)seg.size();
+        if ((size_t)capacity < seg.size()) return VR_ERANGE;
+        for (size_t j = 0; j < seg.size(); ++j) {
+            starts[j] = seg[j].start;
+            classes[j] = seg[j].material_index;
+        }
+        return VR_OK;
+    });
+}
+
 int vr_nifti_read(const char* path, int64_t dims[3], double* cal_max, float* voxels) {
     if (!path || !dims || !cal_max) return VR_EINVAL;
     return guard([&] {
@@ -2559,7 +2699,8 @@ int vr_get_volume_info(vr_ctx* c, vr_volume_info* out) {
     out->zero_transparent = c->zero_transparent;
     uint64_t b = 0;
     for (DevBuf* d : {&c->vol, &c->cls_vrc, &c->cls8, &c->cls_gen, &c->layout_gen, &c->pmaps_gen, &c->pmaps_pad, &c->pmaps_gen_pad, &c->cls_test, &c->maps, &c->pmaps, &c->pmapx64, &c->occ, &c->tf_rgba,
-                      &c->tf_lohi, &c->alpha_nz, &c->frame, &c->counter, &c->layout, &c->egress, &c->occ_test, &c->occ_cols, &c->occ_leafcols, &c->cdist, &c->nrm, &c->tcol, &c->tcc, &c->tcc_lay})
+                      &c->tf_lohi, &c->alpha_nz, &c->frame, &c->counter, &c->layout, &c->egress, &c->occ_test, &c->occ_cols, &c->occ_leafcols, &c->cdist, &c->nrm, &c->tcol, &c->tcc, &c->tcc_lay,
+                      &c->dvr_u8, &c->dvr_minmax, &c->dvr_occ, &c->dvr_start, &c->dvr_seg})
         b += d->bytes;
     out->device_bytes = b;
     out->idx64 = c->idx64 ? 1 : 0;

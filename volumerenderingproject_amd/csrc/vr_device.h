@@ -162,6 +162,21 @@ struct TestFrame {
     float hull[kMaxHull][3];
 };
 
+// The DVR march (vr_dvr.hip) takes its positions, clip, work list, cull and output from a TestFrame
+// (tcb / tnc / occ_words / occ_lds describing its own min/max cells) and adds the classification:
+// the TF as segments of the ordered floats (vr_tf_segments), segment j = [start[j], start[j + 1]).
+constexpr int kDvrSeg8 = 8;                  // up to 1 + 8 segments: the starts past -inf in SGPRs
+constexpr int kMaxDvrSeg = 2 * kMaxTf + 1;   // segments of a TF of kMaxTf intervals
+constexpr int kDvrPad = 64;                  // zero bytes after the byte copy of the volume (dword gathers)
+constexpr int kDvrLdsMax = 64 * 1024;        // LDS budget of a DVR workgroup (tables staged only within it)
+struct DvrFrame {
+    int32_t nseg;               // segments
+    int32_t seg0;               // the segment of the value 0: a sample outside the volume
+    int32_t vol_bytes;          // bytes of the array the corner gathers read (their buffer bound)
+    int32_t reserved;
+    float start[kDvrSeg8];      // nseg <= 9: start[1 .. nseg), the rest NaN (no value is >= NaN)
+};
+
 // TransferFunction::getMaterial (TransferFunction.cu:46-55): last closed interval containing v, else 0
 __device__ __forceinline__ int tf_class(const float* lo, const float* hi, int n, float v) {
     int r = 0;

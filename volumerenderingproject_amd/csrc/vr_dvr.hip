@@ -1,0 +1,415 @@
+// vr_dvr.hip -- VR_MODE_DVR for gfx950: trilinear sample of the scalar field, then TransferFunction
+// classification (interpolate first, classify the interpolated value), and its setup kernels (the
+// byte copy of the volume, the min/max cells, the empty-cell bits).  Its own translation unit so it
+// compiles in parallel with vr_kernels.hip (VRC) and vr_test.hip (TEST).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "vr_device.h"
+#include "vr_march.h"
+
+#pragma clang fp contract(off)
+
+namespace vr {
+
+// a * (1 - w) + b * w on the scalar field, every product and sum rounded on its own.  Classification
+// is discontinuous, so -- unlike TEST's colour lerps -- this is never fused or reassociated, front to
+// back (ERT) included: a one-ulp change of the value could flip a sample's class at a TF boundary.
+__device__ __forceinline__ float lerp1(float a, float b, float w) {
+    const float u = 1.0f - w;
+    return a * u + b * w;
+}
+
+// ------------------------------------------------------------------------------------------------
+// DVR march, one launch per frame, the shape of test_march_kernel: 16 x 16 rays per workgroup (a
+// wave = 8 x 8), work list / background workgroups / hull cull (test_background), TEST's position
+// chain with its per-frame B table in LDS, its linear-model clip and its macro-cell jumps, batches
+// of K = 4 samples whose positions and gathers are all issued before any is used.
+//
+// Per sample inside the volume (0 <= p_a < d_a): corners i0 = (int)p and i1 = min(i0 + 1, d - 1)
+// (clamp to edge), weights p - (int)p, the 8 voxel values lerped in y, then x, then z (TEST's order,
+// kernel.cu:162-175), the result v classified TF((float)((double)v / cal_max)) -- as the count of
+// segment starts <= v (vr_tf_segments: bit for bit that formula, no division) -- and the segment's
+// colour read from the LDS table (the 1-D TF table).  Outside: TF(0).
+//
+// U8: the corner values come from a byte copy of the volume (x-major + kDvrPad zero bytes; built
+// only when every voxel is an integer in 0..255, so the floats are recovered exactly): per (x, y)
+// corner row one unaligned dword at the row's z0 byte, whose low two bytes are the z0 and z0 + 1
+// voxels.  The edge clamp by selects: a row offset of 0 at the last x / y, and at the last z the
+// base byte taken for the neighbour (the dword's second byte is then the next row or the pad).
+// Otherwise eight float gathers from the volume, every index clamped in range; a non-finite voxel
+// reads as 0.
+//
+// SEG8: at most 1 + kDvrSeg8 segments: the starts are wave-uniform kernel arguments (SGPRs) and the
+// segment is the sum of 8 compares (unused starts are NaN: never <= v).  Otherwise a binary search
+// over the starts staged in LDS (kMaxDvrSeg = 513 <= 2^10 - 1: 10 steps).
+//
+// ESS: cells of 2^tcb voxels per axis whose bit in gocc is clear hold no sample with alpha > 0
+// (dvr_cells_kernel); skipping them leaves either blend unchanged bit for bit.
+// ------------------------------------------------------------------------------------------------
+constexpr int kDvrK = 4;
+
+template <bool F2B, bool ESS, bool U8, bool SEG8, bool SEP>
+__global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g, const WorkTile* __restrict__ work,
+                                                        const void* __restrict__ vol,
+                                                        const float* __restrict__ gstart,
+                                                        const float4* __restrict__ gseg,
+                                                        const uint32_t* __restrict__ gocc,
+                                                        float4* __restrict__ out) {
+    constexpr int K = kDvrK;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // LDS: the segments' colours | their starts (search only) | the cell bits (ESS) | the B table (SEP)
+    float4* s_seg = reinterpret_cast<float4*>(smem);
+    float* s_start = reinterpret_cast<float*>(smem + (size_t)g.nseg * sizeof(float4));
+    const bool occ_st = ESS && f.occ_lds;
+    const size_t o_occ = (size_t)g.nseg * sizeof(float4) + (SEG8 ? 0 : ((size_t)g.nseg * 4 + 15) / 16 * 16);
+    uint32_t* s_occ = reinterpret_cast<uint32_t*>(smem + o_occ);
+    float4* s_B = reinterpret_cast<float4*>(smem + o_occ + ((occ_st ? (size_t)f.occ_words * 4 : 0) + 15) / 16 * 16);
+    // first round of loads, unconditional (index clamped, value selected): up to 3 segments and 4
+    // cell words per lane and the work tile; a culled work tile (or a background-only workgroup)
+    // stores the background and leaves before any staging (test_march_kernel)
+    float4 sv[3];
+    float stv[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {   // (nseg <= kMaxDvrSeg = 513 <= 3 * kWgThreads)
+        const int i = (int)threadIdx.x + u * kWgThreads;
+        const int ic = i < g.nseg ? i : 0;
+        sv[u] = gseg[ic];
+        stv[u] = SEG8 ? 0.0f : gstart[ic];
+    }
+    asm volatile("" ::"s"(f.out_tiles), "s"(f.bg_first), "s"(f.n_work), "s"(f.n_hull), "s"(f.W), "s"(f.H));
+    uint32_t ov[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = (int)threadIdx.x + u * kWgThreads;
+        const bool io = occ_st && i < f.occ_words;
+        ov[u] = 0u;
+        if (ESS) { const uint32_t w = gocc[io ? i : 0]; ov[u] = io ? w : 0u; }
+    }
+    const int b = (int)blockIdx.x;
+    const WorkTile wt = work[b < f.n_work ? b : 0];
+    if (b >= f.n_work) return;
+    if (test_background(f, work, wt, out)) return;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+        const int i = (int)threadIdx.x + u * kWgThreads;
+        if (i < g.nseg) {
+            s_seg[i] = sv[u];
+            if (!SEG8) s_start[i] = stv[u];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = (int)threadIdx.x + u * kWgThreads;
+        if (occ_st && i < f.occ_words) s_occ[i] = ov[u];
+    }
+    if (occ_st)
+        for (int i = threadIdx.x + 4 * kWgThreads; i < f.occ_words; i += kWgThreads) s_occ[i] = gocc[i];
+    if (SEP && f.sep_tab) test_stage_B(f, s_B, K);
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t ors = uniform_rsrc(gocc, ESS ? f.occ_words * 4 : 0);
+    auto occ_word = [&](int wi) -> uint32_t {
+        if (f.occ_lds) return s_occ[wi];
+        return __builtin_amdgcn_raw_buffer_load_b32(ors, wi * 4, 0, 0);
+    };
+    // the ERT threshold pinned in a VGPR (test_march_kernel)
+    float ert_eps = f.ert_eps;
+    asm volatile("" : "+v"(ert_eps));
+    int x, y;
+    ray_of_thread(wt, x, y);
+    if (x >= f.W || y >= f.H) return;
+
+    // TEST's position chain, clip and linear model (vr_march.h)
+    TestRay ray;
+    test_ray_init<SEP>(f, x, y, ray);
+    auto position = [&](int s, float p[3]) { test_position<SEP>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
+    int s_begin, s_end;
+    float pa[3], dp[3], idp[3];
+    {
+        float pb[3];
+        position(0, pa);
+        position(f.S > 1 ? f.S - 1 : 0, pb);
+        test_clip(f, pa, pb, dp, idp, s_begin, s_end);
+    }
+
+    const float4 tf0 = s_seg[g.seg0];
+    // (host: the array is addressable with 32-bit byte offsets)
+    const int d3 = (int)f.d3, d23 = (int)(f.d2 * f.d3);
+    const int xl = (int)f.d1 - 1, yl = (int)f.d2 - 1, zl = (int)f.d3 - 1;
+    const __amdgpu_buffer_rsrc_t vrs = uniform_rsrc(vol, g.vol_bytes);
+    float r, gr, bl, T = 1.0f;
+    if (F2B) { r = 0.0f; gr = 0.0f; bl = 0.0f; }
+    else { r = f.bg[0]; gr = f.bg[1]; bl = f.bg[2]; }
+
+    int s = F2B ? s_begin : s_end - 1;
+    bool done = F2B ? (s >= s_end) : (s < s_begin);
+    float pfirst[3];   // ESS: the position of the batch's first sample, from the empty-cell test
+    while (!done) {
+        if (ESS) {
+            float* p = pfirst;
+            position(s, p);
+            // (bitwise, not short-circuit: && chains compile to exec-mask branches)
+            const bool inside = ((int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
+                                 (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
+                                 (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            int cc[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) cc[c] = inside ? ((int)p[c] >> f.tcb) : 0;
+            const int cell = __mul24(__mul24(cc[0], f.tnc[1]) + cc[1], f.tnc[2]) + cc[2];   // (< 2^18 cells)
+            if (inside && !((occ_word(cell >> 5) >> (cell & 31)) & 1u)) {
+                test_cell_jump<F2B>(f, cc, pa, dp, idp, s_begin, s_end, s, done);
+                continue;
+            }
+        }
+        float w[K][3];
+        bool in[K], lastz[K];
+        int off[K][4];
+        bool any_in = false;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int sk = F2B ? s + k : s - k;
+            const bool valid = F2B ? (sk < s_end) : (sk >= s_begin);
+            float p[3];
+            if (ESS && k == 0) {   // (s did not move since the empty-cell test: the same position)
+                p[0] = pfirst[0]; p[1] = pfirst[1]; p[2] = pfirst[2];
+            } else {
+                position(sk, p);
+            }
+            // 0 <= p < fd as unsigned compares of the bits (test_march_kernel)
+            in[k] = ((int)valid & (int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
+                     (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
+                     (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            any_in |= in[k];
+            int i0[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                i0[c] = (int)p[c];
+                // p - (float)(int)p: for an in-volume sample (p >= 0) that is p - floor(p), which
+                // v_fract_f32 returns exactly; outside, unused
+                w[k][c] = __builtin_amdgcn_fractf(p[c]);
+            }
+            // corner rows (x, y) at xy = x << 1 | y; the clamp to edge: no step at the last x / y
+            const int base = i0[0] * d23 + i0[1] * d3 + i0[2];
+            const int ox = i0[0] >= xl ? 0 : d23, oy = i0[1] >= yl ? 0 : d3;
+            off[k][0] = base;
+            off[k][1] = base + oy;
+            off[k][2] = base + ox;
+            off[k][3] = base + ox + oy;
+            lastz[k] = i0[2] >= zl;
+        }
+        // the gathers of the whole batch, exec-masked per sample (lanes outside skip them)
+        uint32_t raw[K][U8 ? 4 : 8];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            if (in[k]) {
+                if (U8) {
+#pragma unroll
+                    for (int xy = 0; xy < 4; ++xy) raw[k][xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy], 0, 0);
+                } else {
+                    const int zs = lastz[k] ? 0 : 4;
+#pragma unroll
+                    for (int xy = 0; xy < 4; ++xy) {
+                        raw[k][2 * xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4, 0, 0);
+                        raw[k][2 * xy + 1] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4 + zs, 0, 0);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < (U8 ? 4 : 8); ++i) raw[k][i] = 0u;
+            }
+        }
+        // a batch with every lane's samples outside the volume composites TF(0) only: with TF(0)
+        // transparent an exact no-op of either blend (f * (1 - 0) + c * 0 = f, T * (1 - 0) = T)
+        const bool blank = f.zero_transparent && !__any(any_in);
+        if (!blank) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                float c[8];   // corner kk = x << 2 | y << 1 | z
+#pragma unroll
+                for (int xy = 0; xy < 4; ++xy) {
+                    if (U8) {
+                        const uint32_t z0 = raw[k][xy] & 0xffu, z1 = (raw[k][xy] >> 8) & 0xffu;
+                        c[2 * xy] = (float)z0;
+                        c[2 * xy + 1] = (float)(lastz[k] ? z0 : z1);
+                    } else {
+#pragma unroll
+                        for (int z = 0; z < 2; ++z) {   // a non-finite voxel reads as 0
+                            const uint32_t u = raw[k][2 * xy + z];
+                            c[2 * xy + z] = (u & 0x7f800000u) == 0x7f800000u ? 0.0f : __uint_as_float(u);
+                        }
+                    }
+                }
+                const float dx = w[k][0], dy = w[k][1], dz = w[k][2];
+                const float y1 = lerp1(c[0], c[2], dy), y2 = lerp1(c[1], c[3], dy);
+                const float y3 = lerp1(c[4], c[6], dy), y4 = lerp1(c[5], c[7], dy);
+                const float z1 = lerp1(y1, y3, dx), z2 = lerp1(y2, y4, dx);
+                const float v = lerp1(z1, z2, dz);
+                int seg = 0;
+                if (SEG8) {
+#pragma unroll
+                    for (int j = 0; j < kDvrSeg8; ++j) seg += (int)(v >= g.start[j]);
+                } else {
+                    // the last start <= v (start[0] = -inf; a NaN stays in segment 0)
+#pragma unroll
+                    for (int step = 512; step >= 1; step >>= 1) {
+                        const int np = seg + step;
+                        const float st = s_start[min(np, g.nseg - 1)];
+                        seg = (np < g.nseg && v >= st) ? np : seg;
+                    }
+                }
+                const float4 cs = s_seg[seg];
+                const float4 cf = in[k] ? cs : tf0;
+                const int sk = F2B ? s + k : s - k;
+                const float a = (F2B ? (sk < s_end) : (sk >= s_begin)) ? cf.w : 0.0f;
+                if (F2B) {
+                    const float wt_ = T * a;
+                    r = fmaf(wt_, cf.x, r); gr = fmaf(wt_, cf.y, gr); bl = fmaf(wt_, cf.z, bl);
+                    T = T * (1.0f - a);
+                } else {
+                    r = r * (1 - a) + cf.x * a;
+                    gr = gr * (1 - a) + cf.y * a;
+                    bl = bl * (1 - a) + cf.z * a;
+                }
+            }
+        }
+        if (F2B && T < ert_eps) done = true;
+        s = F2B ? s + K : s - K;
+        if (F2B ? (s >= s_end) : (s < s_begin)) done = true;
+    }
+    if (F2B) { r = r + T * f.bg[0]; gr = gr + T * f.bg[1]; bl = bl + T * f.bg[2]; }
+    store_pixel(out, out_index(f.out_tiles, wt, x, y, f.H, f.tile_w, f.tile_h), f.out_rgb, r, gr, bl);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Setup kernels (first DVR frame of a context; dvr_cells_kernel again on every TF change)
+// ------------------------------------------------------------------------------------------------
+
+// The byte copy of the volume; flag[0] = 1 when a voxel is not an integer in 0..255 (the copy is
+// then lossy and not used).  Every writer stores the same value (plain vector stores, no atomics).
+__global__ __launch_bounds__(256) void dvr_bytes_kernel(const float* __restrict__ vol, int64_t n,
+                                                        uint8_t* __restrict__ out, int32_t* __restrict__ flag) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v = vol[i];
+        const bool ok = v >= 0.0f && v <= 255.0f && (float)(int)v == v;
+        out[i] = ok ? (uint8_t)(int)v : (uint8_t)0;
+        if (!ok) flag[0] = 1;
+    }
+}
+
+// Min / max level of the cells: cell (cx, cy, cz) covers voxels [c B, c B + B] per axis, B = 2^tcb,
+// clamped to d - 1 -- every corner a sample based in the cell ((int)p in [c B, c B + B)) can read,
+// its clamped + 1 neighbours included (the role of the reference's Node{max, min}).  Non-finite
+// voxels count as the 0 they read as.
+__global__ __launch_bounds__(256) void dvr_minmax_kernel(const float* __restrict__ vol, int64_t d1, int64_t d2,
+                                                         int64_t d3, int tcb, int nc1, int nc2, int nc3,
+                                                         float2* __restrict__ mm) {
+    const int64_t ncells = (int64_t)nc1 * nc2 * nc3;
+    const int64_t cell = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (cell >= ncells) return;
+    const int c[3] = {(int)(cell / ((int64_t)nc2 * nc3)), (int)((cell / nc3) % nc2), (int)(cell % nc3)};
+    const int64_t d[3] = {d1, d2, d3};
+    int64_t lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = (int64_t)c[a] << tcb;
+        hi[a] = lo[a] + ((int64_t)1 << tcb);
+        hi[a] = hi[a] < d[a] - 1 ? hi[a] : d[a] - 1;
+    }
+    float mn = 3.4e38f, mx = -3.4e38f;
+    for (int64_t x = lo[0]; x <= hi[0]; ++x)
+        for (int64_t y = lo[1]; y <= hi[1]; ++y) {
+            const float* row = vol + (x * d2 + y) * d3;
+            for (int64_t z = lo[2]; z <= hi[2]; ++z) {
+                float v = row[z];
+                if ((__float_as_uint(v) & 0x7f800000u) == 0x7f800000u) v = 0.0f;
+                mn = fminf(mn, v);
+                mx = fmaxf(mx, v);
+            }
+        }
+    mm[cell] = make_float2(mn, mx);
+}
+
+// Cell bits: a cell is empty (bit clear) iff every segment meeting [min - m, max + m] has alpha 0,
+// m = 2^-20 max(|min|, |max|).  The margin: the march's unfused lerp a (1 - w) + b w of values in
+// [min, max] can leave that range.  fl(1 - w) is off by <= 2^-25 (half an ulp below 1), each of the
+// two products and the sum rounds once (<= 2^-24 relative each), so one level ends at most ~2 ulps
+// outside the range of its inputs, and the three levels (y, x, z) under ~6 ulps = 6 * 2^-23
+// relative to the larger magnitude; 2^-20 relative is 8 ulps.  (All eight corners equal to
+// float32(0.1): 11 % of random weights give a value one ulp above 0.1.)  A margin too wide only
+// keeps a cell that could have been skipped.
+__global__ __launch_bounds__(256) void dvr_cells_kernel(const float2* __restrict__ mm, int64_t ncells,
+                                                        const float* __restrict__ start,
+                                                        const float4* __restrict__ seg, int nseg,
+                                                        unsigned long long* __restrict__ occ) {
+    const int64_t cell = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool occupied = false;
+    if (cell < ncells) {
+        const float2 r = mm[cell];
+        const float m = fmaxf(fabsf(r.x), fabsf(r.y)) * 9.5367431640625e-07f;   // 2^-20
+        const float lo = r.x - m, hi = r.y + m;
+        for (int j = 0; j < nseg; ++j) {
+            // segment j = [start[j], start[j + 1]), the last one to +inf
+            const bool meets = start[j] <= hi && (j + 1 == nseg || start[j + 1] > lo);
+            occupied = occupied || (meets && seg[j].w != 0.0f);
+        }
+    }
+    const unsigned long long mask = __ballot(occupied);
+    if ((threadIdx.x & 63) == 0 && cell < ncells) occ[cell >> 6] = mask;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Launch wrappers (called from vr_api.cpp)
+// ------------------------------------------------------------------------------------------------
+
+// LDS bytes of a DVR workgroup (host: the B table is dropped when the sum would pass kDvrLdsMax)
+size_t dvr_lds_bytes(const TestFrame& f, const DvrFrame& g, bool ess) {
+    const bool seg8 = g.nseg <= 1 + kDvrSeg8;
+    return (size_t)g.nseg * sizeof(float4) + (seg8 ? 0 : ((size_t)g.nseg * 4 + 15) / 16 * 16) +
+           (((ess && f.occ_lds) ? (size_t)f.occ_words * 4 : 0) + 15) / 16 * 16 +
+           ((f.sep && f.sep_tab) ? (size_t)(f.S + 2 * kDvrK) * sizeof(float4) : 0);
+}
+
+hipError_t launch_dvr_march(const TestFrame& f, const DvrFrame& g, const WorkTile* work, int n_blocks, const void* vol,
+                            bool u8, const float* start, const float4* seg, const uint32_t* occ, float4* out,
+                            hipStream_t st) {
+    const bool f2b = (f.flags & 2) != 0, ess = (f.flags & 1) != 0 && f.zero_transparent && occ != nullptr;
+    const bool seg8 = g.nseg <= 1 + kDvrSeg8, sep = f.sep != 0;
+    const size_t lds = dvr_lds_bytes(f, g, ess);
+#define VR_D5(F2B_, ESS_, U8_, SEG8_, SEP_)                                                                     \
+    hipLaunchKernelGGL((dvr_march_kernel<F2B_, ESS_, U8_, SEG8_, SEP_>), dim3(n_blocks), dim3(kWgThreads), lds, \
+                       st, f, g, work, vol, start, seg, occ, out)
+#define VR_D4(F2B_, ESS_, U8_, SEG8_) do { if (sep) VR_D5(F2B_, ESS_, U8_, SEG8_, true); else VR_D5(F2B_, ESS_, U8_, SEG8_, false); } while (0)
+#define VR_D3(F2B_, ESS_, U8_) do { if (seg8) VR_D4(F2B_, ESS_, U8_, true); else VR_D4(F2B_, ESS_, U8_, false); } while (0)
+#define VR_D2(F2B_, ESS_) do { if (u8) VR_D3(F2B_, ESS_, true); else VR_D3(F2B_, ESS_, false); } while (0)
+    if (f2b) { if (ess) VR_D2(true, true); else VR_D2(true, false); }
+    else { if (ess) VR_D2(false, true); else VR_D2(false, false); }
+#undef VR_D2
+#undef VR_D3
+#undef VR_D4
+#undef VR_D5
+    return hipGetLastError();
+}
+
+hipError_t launch_dvr_bytes(const float* vol, int64_t n, uint8_t* out, int32_t* flag, hipStream_t st) {
+    const int blocks = (int)std::min<int64_t>((n + 255) / 256, 256 * 64);
+    hipLaunchKernelGGL(dvr_bytes_kernel, dim3(blocks), dim3(256), 0, st, vol, n, out, flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_dvr_minmax(const float* vol, int64_t d1, int64_t d2, int64_t d3, int tcb, int nc1, int nc2, int nc3,
+                             float2* mm, hipStream_t st) {
+    const int64_t ncells = (int64_t)nc1 * nc2 * nc3;
+    hipLaunchKernelGGL(dvr_minmax_kernel, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, st, vol, d1, d2, d3, tcb,
+                       nc1, nc2, nc3, mm);
+    return hipGetLastError();
+}
+
+hipError_t launch_dvr_cells(const float2* mm, int64_t ncells, const float* start, const float4* seg, int nseg,
+                            unsigned long long* occ, hipStream_t st) {
+    hipLaunchKernelGGL(dvr_cells_kernel, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, st, mm, ncells, start,
+                       seg, nseg, occ);
+    return hipGetLastError();
+}
+
+}  // namespace vr

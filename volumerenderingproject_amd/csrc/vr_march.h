@@ -1,5 +1,5 @@
 // vr_march.h -- device helpers shared by the march kernels (vr_kernels.hip: VRC and the setup
-// kernels; vr_test.hip: TEST).  Internal, not the ABI.
+// kernels; vr_test.hip: TEST; vr_dvr.hip: DVR).  Internal, not the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -116,6 +116,190 @@ __device__ __forceinline__ void axis_leaf_column(const VrcFrame& f, int ma, cons
     i0 = (int)min((unsigned)(int)(q0 * f.leaves), lim);
     i1 = (int)min((unsigned)(int)(q1 * f.leaves), lim);
     in_cube = ((int)in_unit(q0) & (int)in_unit(q1)) != 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Sample positions of TEST (kernel.cu:100-115) as functions, for the DVR march: a DVR frame registers
+// with the TEST frame of the same camera sample for sample.  The same expressions in the same order
+// as test_march_kernel (vr_test.hip; the derivations are there), which keeps its own text because
+// calling these moved its register allocation (C3 oblique ESS + ERT 0.176 -> 0.181 ms); both are held
+// to the oracle's positions bit for bit (tests/test_gpu_test_mode.py, tests/test_gpu_dvr.py through
+// tests/test_dvr_ref.py).  mulv3 and test_background are shared by both.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void mulv3(const float* m, float x, float y, float z, float o[3]) {
+    // glm mat4 * vec4(x, y, z, 1): (m0*x + m1*y) + (m2*z + m3*1), w dropped (vec3 truncation)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const float a0 = m[0 + r] * x + m[4 + r] * y;
+        const float a1 = m[8 + r] * z + m[12 + r] * 1.0f;
+        o[r] = a0 + a1;
+    }
+}
+
+// The per-ray half of the position chain: Add0 = m0*x + m1*y of the first product and, SEP
+// (modelCam and toVolume are scales + translations), A_r = iv_r q1x + iv_{4+r} q1y.
+struct TestRay {
+    float add0[3], A[3];
+};
+template <bool SEP>
+__device__ __forceinline__ void test_ray_init(const TestFrame& f, int x, int y, TestRay& ray) {
+    const float fx = (float)x, fy = (float)y;
+    // first product, split: Add0 = m0*x + m1*y per ray; Add1 = m2*s + m3 per sample
+#pragma unroll
+    for (int r = 0; r < 3; ++r) ray.add0[r] = f.mc[0 + r] * fx + f.mc[4 + r] * fy;
+    // SEP (always, for the matrices kernel.cu:1177-1216 builds: modelCam and toVolume are scales +
+    // translations): the zero entries of mc and tv contribute exact zeros to glm's
+    // (m0*x + m1*y) + (m2*z + m3) (x + 0 = x, and a zero's sign cannot reach a frame value), so
+    // q1 = (mc0*x + mc12, mc5*y + mc13, mc10*s + mc14) and p_r = tv_rr * q2_r + tv_3r bit for bit.
+    // inverse(lookAt) is general, but its first pair iv_r*q1x + iv_4+r*q1y only depends on the
+    // ray: per sample 17 operations instead of 51, the same roundings in the same order.
+    if (SEP) {
+        const float q1x = f.mc[0] * fx + f.mc[12], q1y = f.mc[5] * fy + f.mc[13];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) ray.A[r] = f.iv[r] * q1x + f.iv[4 + r] * q1y;
+    }
+}
+
+// SEP: the per-sample half of the second product, B_r(s) = iv_{8+r} q1z(s) + iv_{12+r} with
+// q1z(s) = mc10 s + mc14, is the same for every ray: entry j of the per-frame LDS table (sample
+// s = j - K, for s in [-K, S + K))
+__device__ __forceinline__ float4 test_B_entry(const TestFrame& f, float fs) {
+    const float q1z = f.mc[10] * fs + f.mc[14];
+    return make_float4(f.iv[8] * q1z + f.iv[12] * 1.0f, f.iv[9] * q1z + f.iv[13] * 1.0f,
+                       f.iv[10] * q1z + f.iv[14] * 1.0f, 0.0f);
+}
+__device__ __forceinline__ void test_stage_B(const TestFrame& f, float4* s_B, int K) {
+    for (int j = threadIdx.x; j < f.S + 2 * K; j += kWgThreads) s_B[j] = test_B_entry(f, (float)(j - K));
+}
+
+// p = T * (V * (Mcam * (x, y, s, 1))) for sample s in [-K, S + K); tab: B_r(s) from the LDS table
+// (without it -- long rays: it would not fit LDS -- the same expressions per sample)
+template <bool SEP>
+__device__ __forceinline__ void test_position(const TestFrame& f, const TestRay& ray, const float4* s_B, bool tab,
+                                              int K, int s, float p[3]) {
+    const float fs = (float)s;
+    if (SEP) {
+        float4 Bs;
+        if (tab) Bs = s_B[s + K];
+        else Bs = test_B_entry(f, fs);
+        float q2[3];
+        q2[0] = ray.A[0] + Bs.x;
+        q2[1] = ray.A[1] + Bs.y;
+        q2[2] = ray.A[2] + Bs.z;
+        p[0] = f.tv[0] * q2[0] + f.tv[12];
+        p[1] = f.tv[5] * q2[1] + f.tv[13];
+        p[2] = f.tv[10] * q2[2] + f.tv[14];
+        return;
+    }
+    float q1[3], q2[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) q1[r] = ray.add0[r] + (f.mc[8 + r] * fs + f.mc[12 + r] * 1.0f);
+    mulv3(f.iv, q1[0], q1[1], q1[2], q2);
+    mulv3(f.tv, q2[0], q2[1], q2[2], p);
+}
+
+// The ray's linear model p(s) ~= pa + s dp (from its exact end points pa = p(0), pb = p(S - 1)) and its
+// conservative clip to the volume widened by 0.01 voxel: samples outside [s_begin, s_end) are outside
+// the volume, TF(0), alpha 0 (zero_transparent).  In float: p(s) itself departs from the line by a
+// few ulps of |p| (~1e-5 voxel), the float quotients by ~1e-7 of s (< 1e-3 samples at S = 9k) -- far
+// inside the 0.01-voxel and floor - 1 / ceil + 2 margins.  A zero step tests the point; a denormal
+// one gives an infinite reciprocal, whose products keep the test conservative (a NaN from 0 * inf
+// is ignored by fminf / fmaxf: no constraint).
+__device__ __forceinline__ void test_clip(const TestFrame& f, const float pa[3], const float pb[3], float dp[3],
+                                          float idp[3], int& s_begin, int& s_end) {
+    s_begin = 0;
+    s_end = f.S;
+    const float dims[3] = {f.fd1, f.fd2, f.fd3};
+    const float den = (float)(f.S > 1 ? f.S - 1 : 1);
+    float a = 0.0f, bnd = (float)(f.S - 1);
+    bool off = false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        dp[c] = f.S > 1 ? (pb[c] - pa[c]) / den : 0.0f;
+        idp[c] = dp[c] != 0.0f ? 1.0f / dp[c] : 0.0f;
+        const float lo = -0.01f, hi = dims[c] + 0.01f;
+        if (dp[c] == 0.0f) {
+            off |= (pa[c] < lo) | (pa[c] > hi);
+        } else {
+            const float t0 = (lo - pa[c]) * idp[c], t1 = (hi - pa[c]) * idp[c];
+            a = fmaxf(a, fminf(t0, t1));
+            bnd = fminf(bnd, fmaxf(t0, t1));
+        }
+    }
+    if (f.zero_transparent) {
+        if (off || !(a <= bnd)) {
+            s_end = 0;
+        } else {
+            s_begin = max(0, (int)floorf(a) - 1);
+            s_end = min(f.S, (int)ceilf(bnd) + 2);
+        }
+    }
+}
+
+// ESS: sample s lies in the empty macro cell cc (2^tcb voxels per axis): the next sample in march
+// order past the cell, from the linear model with a 0.05-voxel safety margin (which covers the
+// model's rounding), so every skipped sample lies inside the cell.
+template <bool F2B>
+__device__ __forceinline__ void test_cell_jump(const TestFrame& f, const int cc[3], const float pa[3],
+                                               const float dp[3], const float idp[3], int s_begin, int s_end, int& s,
+                                               bool& done) {
+    float sstar = F2B ? 3.0e38f : -3.0e38f;
+    const float B = (float)(1 << f.tcb);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (dp[c] == 0.0f) continue;
+        const bool up_axis = F2B ? (dp[c] > 0.0f) : (dp[c] < 0.0f);
+        const float bound = up_axis ? (float)(cc[c] + 1) * B - 0.05f : (float)cc[c] * B + 0.05f;
+        const float sc = (bound - pa[c]) * idp[c];   // (the 0.05-voxel margin covers the rounding)
+        sstar = F2B ? fminf(sstar, sc) : fmaxf(sstar, sc);
+    }
+    if (F2B) {
+        const float nx = ceilf(sstar);
+        s = nx > (float)(s + 1) ? (nx < (float)f.S ? (int)nx : f.S) : s + 1;
+        done = s >= s_end;
+    } else {
+        const float nx = floorf(sstar);
+        s = nx < (float)(s - 1) ? (nx > -1.0f ? (int)nx : -1) : s - 1;
+        done = s < s_begin;
+    }
+}
+
+// Whole TEST and DVR frames: work tiles off the dataset box's projection (vr_api.cpp project_box_test) are
+// exactly the background; a background-only workgroup (blockIdx >= bg_first) stores bg_group of
+// them, and a culled tile (slot < 0) among the marching ones stores its own -- both before any
+// staging.  True if this workgroup is done.  (vr_test.hip, vr_dvr.hip)
+__device__ __forceinline__ bool test_background(const TestFrame& f, const WorkTile* __restrict__ work, const WorkTile& wt,
+                                                float4* __restrict__ out) {
+    if (f.out_tiles) return false;
+    const float4 bg = make_float4(f.bg[0], f.bg[1], f.bg[2], 1.0f);
+    if ((int)blockIdx.x >= f.bg_first) {
+        const int e0 = f.bg_first + ((int)blockIdx.x - f.bg_first) * f.bg_group;
+        for (int i = 0; i < f.bg_group; ++i) {
+            const int e = e0 + i;
+            if (e >= f.n_work) break;
+            int x, y;
+            ray_of_thread(work[e], x, y);
+            if (x < f.W && y < f.H) store_f4(out + (int64_t)x * f.H + y, bg);
+        }
+        return true;
+    }
+    bool off = wt.slot < 0;
+    // general views: a work tile inside the visible rectangle but off the projected box's hull
+    // (separated by one of its edges, vr_api.cpp hull_edges) sees only TF(0): the background too.
+    // Wave-uniform: the tile's pixels [x0, x0 + 16) x [y0, y0 + 16) against each edge's half-plane.
+    // (unrolled over kMaxHull so the edges' kernel-argument loads issue together)
+#pragma unroll
+    for (int e = 0; e < kMaxHull; ++e) {
+        const float nx = f.hull[e][0], ny = f.hull[e][1];
+        const float px = (float)wt.x0 + (nx > 0.0f ? 0.0f : (float)(kWgRaysX - 1));
+        const float py = (float)wt.y0 + (ny > 0.0f ? 0.0f : (float)(kWgRaysY - 1));
+        off |= (e < f.n_hull) & (nx * px + ny * py > f.hull[e][2]);   // (bitwise: no branch per edge)
+    }
+    if (!off) return false;
+    int x, y;
+    ray_of_thread(wt, x, y);
+    if (x < f.W && y < f.H) store_f4(out + (int64_t)x * f.H + y, bg);
+    return true;
 }
 
 // Counting passes (vr_count_work, never a timed launch): a lane's class gathers that touched memory,

@@ -17,16 +17,6 @@ namespace vr {
 // ------------------------------------------------------------------------------------------------
 // TEST march: fused getColorFromNF + blendSampleColors (kernel.cu:72-187, :194-225).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void mulv3(const float* m, float x, float y, float z, float o[3]) {
-    // glm mat4 * vec4(x, y, z, 1): (m0*x + m1*y) + (m2*z + m3*1), w dropped (vec3 truncation)
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const float a0 = m[0 + r] * x + m[4 + r] * y;
-        const float a1 = m[8 + r] * z + m[12 + r] * 1.0f;
-        o[r] = a0 + a1;
-    }
-}
-
 // a * (1 - w) + b * w (kernel.cu:162-175).  The exact (back-to-front) march evaluates it as written,
 // every product and sum rounded (the contraction-off model of the whole restatement, oracle/), so
 // exact TEST frames are bitwise the oracle's; the fast front-to-back march fuses the second product
@@ -61,43 +51,8 @@ __device__ __forceinline__ float4 lerp4(float4 a, float4 b, float w) {
 // corner indices wrap, are always occupied.  Jumps use the linear model p(s) ~ pa + s*dp with a
 // 0.05-voxel safety margin, so every skipped sample lies inside the empty cell.
 //
-// Whole TEST frames: work tiles off the dataset box's projection (vr_api.cpp project_box_test) are
-// exactly the background; a background-only workgroup (blockIdx >= bg_first) stores bg_group of
-// them, and a culled tile (slot < 0) among the marching ones stores its own -- both before any
-// staging.  True if this workgroup is done.
-__device__ __forceinline__ bool test_background(const TestFrame& f, const WorkTile* __restrict__ work, const WorkTile& wt,
-                                                float4* __restrict__ out) {
-    if (f.out_tiles) return false;
-    const float4 bg = make_float4(f.bg[0], f.bg[1], f.bg[2], 1.0f);
-    if ((int)blockIdx.x >= f.bg_first) {
-        const int e0 = f.bg_first + ((int)blockIdx.x - f.bg_first) * f.bg_group;
-        for (int i = 0; i < f.bg_group; ++i) {
-            const int e = e0 + i;
-            if (e >= f.n_work) break;
-            int x, y;
-            ray_of_thread(work[e], x, y);
-            if (x < f.W && y < f.H) store_f4(out + (int64_t)x * f.H + y, bg);
-        }
-        return true;
-    }
-    bool off = wt.slot < 0;
-    // general views: a work tile inside the visible rectangle but off the projected box's hull
-    // (separated by one of its edges, vr_api.cpp hull_edges) sees only TF(0): the background too.
-    // Wave-uniform: the tile's pixels [x0, x0 + 16) x [y0, y0 + 16) against each edge's half-plane.
-    // (unrolled over kMaxHull so the edges' kernel-argument loads issue together)
-#pragma unroll
-    for (int e = 0; e < kMaxHull; ++e) {
-        const float nx = f.hull[e][0], ny = f.hull[e][1];
-        const float px = (float)wt.x0 + (nx > 0.0f ? 0.0f : (float)(kWgRaysX - 1));
-        const float py = (float)wt.y0 + (ny > 0.0f ? 0.0f : (float)(kWgRaysY - 1));
-        off |= (e < f.n_hull) & (nx * px + ny * py > f.hull[e][2]);   // (bitwise: no branch per edge)
-    }
-    if (!off) return false;
-    int x, y;
-    ray_of_thread(wt, x, y);
-    if (x < f.W && y < f.H) store_f4(out + (int64_t)x * f.H + y, bg);
-    return true;
-}
+// (mulv3 and test_background -- whole frames' background-only workgroups and culled work tiles -- are
+// shared with the DVR march: vr_march.h)
 
 // CV = the corner volume a sample's 8 corner classes come from in ONE gather (host: class 0 = TF(0),
 // 32-bit offsets): 0 none (four corner-row dwords of the class volume); CB = 2 / 4 / 8 bits per
@@ -256,6 +211,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PT ? VR_TES
         for (int r = 0; r < 3; ++r) A[r] = f.iv[r] * q1x + f.iv[4 + r] * q1y;
     }
 
+    // (vr_march.h restates this chain, the clip and the cell jump below as functions for the DVR march;
+    // this kernel keeps its own text -- calling them moved its register allocation and cost the C3
+    // oblique march 2.4 % -- and tests pin both to the oracle's positions: keep the two in step)
     auto position = [&](int s, float p[3]) {
         const float fs = (float)s;
         if (SEP) {

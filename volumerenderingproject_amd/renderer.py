@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("VR_LIB") or os.path.join(_HERE, "libvr.so")   # VR_LI
 VR_OK = 0
 VR_MODE_VRC = 1
 VR_MODE_TEST = 5
+VR_MODE_DVR = 6       # trilinear sample of the scalar field, then TF classification
 VR_FLAG_ESS = 1
 VR_FLAG_ERT = 2
 VR_FLAG_SHADE = 8
@@ -41,7 +42,7 @@ EXPORTED = [
     "vr_assemble_tile_slots_multi", "vr_options_default", "vr_create_ex", "vr_get_options", "vr_set_options",
     "vr_create_multi", "vr_comm_unique_id", "vr_create_rank", "vr_group_info", "vr_group_tiles", "vr_render_png",
     "vr_render_batch", "vr_create_multi_ex", "vr_group_timing_read", "vr_count_work", "vr_group_traffic_read",
-    "vr_axis_columns_plan",
+    "vr_axis_columns_plan", "vr_tf_segments",
 ]
 VR_COMM_ID_BYTES = 128
 VR_TRANSPORT_NONE, VR_TRANSPORT_RCCL, VR_TRANSPORT_PEER_COPY = 0, 1, 2
@@ -111,7 +112,8 @@ class Options(C.Structure):
                 ("table_split", C.c_int32),
                 ("test_corners", C.c_int32),
                 ("leaf_columns", C.c_int32),
-                ("axis_columns", C.c_int32)]
+                ("axis_columns", C.c_int32),
+                ("dvr_volume", C.c_int32)]
 
 
 class WorkCount(C.Structure):
@@ -175,6 +177,8 @@ def lib():
         "vr_count_marched": ([vp, P(RenderParams), P(Camera), P(C.c_uint64), P(C.c_uint64)], C.c_int),
         "vr_count_work": ([vp, P(RenderParams), P(Camera), P(WorkCount)], C.c_int),
         "vr_axis_columns_plan": ([vp, P(RenderParams), P(Camera), P(C.c_int32)], C.c_int),
+        "vr_tf_segments": ([P(TFInterval), C.c_int32, C.c_double, P(C.c_float), P(C.c_int32), C.c_int32,
+                            P(C.c_int32)], C.c_int),
         "vr_synchronize": ([vp], C.c_int),
         "vr_set_stream": ([vp, vp], C.c_int),
         "vr_params_default": ([C.c_int32, C.c_int32, C.c_int32, P(RenderParams)], C.c_int),
@@ -296,6 +300,20 @@ def _tf_array(tf):
         for c in range(4):
             arr[i].rgba[c] = rgba[c]
     return arr
+
+
+def tf_segments(tf, cal_max):
+    """vr_tf_segments (no GPU): the classes of (float)((double)v / cal_max) over the ordered floats v as
+    (starts float32 [n], classes int32 [n]); segment j holds starts[j] <= v < starts[j + 1], starts[0] is
+    -inf, neighbouring segments differ in class."""
+    arr = _tf_array(tf)
+    cap = 2 * len(tf) + 1
+    starts = np.empty(cap, np.float32)
+    classes = np.empty(cap, np.int32)
+    n = C.c_int32(0)
+    _check(lib().vr_tf_segments(arr, len(tf), float(cal_max), starts.ctypes.data_as(C.POINTER(C.c_float)),
+                                classes.ctypes.data_as(C.POINTER(C.c_int32)), cap, C.byref(n)), "vr_tf_segments")
+    return starts[:n.value].copy(), classes[:n.value].copy()
 
 
 def nifti_read(path):
