@@ -97,7 +97,10 @@ typedef struct {
 } vr_tf_interval;
 
 /* AppData render fields (utils.h:36-74) made runtime.  vr_params_default fills the reference's
- * values for a given W, H, S. */
+ * values for a given W, H, S.  Every finite value is defined: a zero or negative sample_distance
+ * (VRC: S copies of one point / the march runs backwards) and viewplane_distance (TEST, DVR) render
+ * the reference's arithmetic as written.  background[3] is ignored: a frame's alpha is 1
+ * (kernel.cu:213).  VRC normalises by (float)(int)cal_max, TEST and DVR by the double cal_max. */
 typedef struct {
     int32_t width, height, samples_per_ray, mode, flags;
     float real_screen_width, real_screen_height, viewplane_distance, front_clip_plane,
@@ -345,7 +348,9 @@ int vr_render_tile_list(vr_ctx* ctx, const vr_params* params, const vr_camera* c
                         int32_t stride, float* d_tiles, int32_t* n_tiles_out, int32_t out_flags);
 
 /* Assembly for a tile list: block k of rank r in d_tiles (max_tiles_per_rank blocks per rank)
- * holds tile tiles[r + k*n_ranks]; every pixel of a tile not in the list is set to background. */
+ * holds tile tiles[r + k*n_ranks]; every pixel of a tile not in the list is set to background's
+ * r, g, b with alpha 1 (what the march stores there; background[3] is ignored, here and in the
+ * two assemblies below). */
 int vr_assemble_tile_list(vr_ctx* ctx, int32_t width, int32_t height, int32_t tile_w, int32_t tile_h,
                           const int32_t* tiles, int32_t n_tiles, int32_t n_ranks,
                           int32_t max_tiles_per_rank, const float* d_tiles, const float background[4],

@@ -1824,6 +1824,12 @@ void render_tile_list(vr_ctx* c, const vr_params* p, const vr_camera* cam, int t
     launch_frame(c, p, cam, wc, reinterpret_cast<float4*>(d_tiles), 1, tile_w, tile_h, out_rgb);
 }
 
+// The pixel the tile assemblies write where no tile was rendered: the background's colour with
+// alpha 1, which is what the march stores there (background[3] is ignored, as in vr_params)
+float4 assembly_background(const float background[4]) {
+    return make_float4(background[0], background[1], background[2], 1.0f);
+}
+
 void assemble_slots(vr_ctx* c, int W, int H, int tile_w, int tile_h, const std::vector<int32_t>& tiles,
                     const std::vector<int32_t>& slots, int n_blocks, const float* d_tiles, const float background[4],
                     float* d_frame, int out_rgb) {
@@ -1855,7 +1861,7 @@ void assemble_slots(vr_ctx* c, int W, int H, int tile_w, int tile_h, const std::
         c->slot_maps[std::move(key)] = std::move(b);
     }
     hip_check(launch_assemble_list(W, H, tile_w, tile_h, map->as<int32_t>(), reinterpret_cast<const float4*>(d_tiles),
-                                   make_float4(background[0], background[1], background[2], background[3]),
+                                   assembly_background(background),
                                    reinterpret_cast<float4*>(d_frame), out_rgb, c->stream));
 }
 
@@ -2306,7 +2312,7 @@ int vr_assemble_tile_list(vr_ctx* c, int32_t W, int32_t H, int32_t tile_w, int32
         }
         hip_check(launch_assemble_list(W, H, tile_w, tile_h, map->as<int32_t>(),
                                        reinterpret_cast<const float4*>(d_tiles),
-                                       make_float4(background[0], background[1], background[2], background[3]),
+                                       assembly_background(background),
                                        reinterpret_cast<float4*>(d_frame), (out_flags & VR_OUT_RGB) ? 1 : 0, c->stream));
         if (!(out_flags & VR_OUT_ASYNC)) hip_check(hipStreamSynchronize(c->stream));
         return VR_OK;
@@ -2350,7 +2356,7 @@ int vr_assemble_tile_slots_multi(vr_ctx* c, int32_t W, int32_t H, int32_t tile_w
         }
         hip_check(launch_assemble_list(W, H, tile_w, tile_h, map->as<int32_t>(),
                                        reinterpret_cast<const float4*>(d_tiles),
-                                       make_float4(background[0], background[1], background[2], background[3]),
+                                       assembly_background(background),
                                        reinterpret_cast<float4*>(d_frames), (out_flags & VR_OUT_RGB) ? 1 : 0, c->stream,
                                        n_frames));
         if (!(out_flags & VR_OUT_ASYNC)) hip_check(hipStreamSynchronize(c->stream));
