@@ -1,11 +1,13 @@
 """Volumes, views, parameter cases and reference calls off the defaults -- TEST INFRASTRUCTURE ONLY.
 
 Shared by tests/test_param_cases.py (CPU: the cases are not vacuous) and tests/test_gpu_params.py /
-tests/test_gpu_volumes.py (GPU: the library against the references), so the three cannot drift apart.
+tests/test_gpu_volumes.py / tests/test_gpu_shade.py (GPU: the library against the references), so
+they cannot drift apart.
 Importing this module needs neither a GPU nor libvr.so: the library's cameras and parameters are
 built on first use (gpu_camera, gpu_params).
 
-References: VRC is the oracle's octree march (OracleOctree.render_vrc), TEST oracle.render_test, DVR
+References: VRC is the oracle's octree march (OracleOctree.render_vrc; render_vrc_shaded for a case
+with shading coefficients), TEST oracle.render_test, DVR
 tests/dvr_ref.py.  A volume with non-finite voxels takes the closed-form octree (implicit=True): the
 literal tree's search recurses past its leaves when max == min is false (NaN), the closed form
 returns x > 0 ? x : 0 -- what the library's classify kernel states -- and equals the literal tree bit
@@ -18,7 +20,7 @@ import oracle
 
 F = np.float32
 VRC, TEST, DVR = 1, 5, 6          # vr_api.h VR_MODE_*
-CONIC = 16                        # vr_api.h VR_FLAG_CONIC
+SHADE, CONIC = 8, 16              # vr_api.h VR_FLAG_SHADE, VR_FLAG_CONIC
 MODES = {"vrc": VRC, "test": TEST, "dvr": DVR}
 
 W, H, S = 48, 36, 64              # the frame of every case but the tiny shapes
@@ -32,8 +34,10 @@ VIEWS = {
     "x": ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0)),
     "y_back": ((0.0, -1.0, 0.0), (0.0, 0.0, 1.0)),
     "obl": ((0.6, 0.5, 0.7), (0.0, 1.0, 0.0)),
+    "x_back": ((-1.0, 0.0, 0.0), (0.0, 1.0, 0.0)),
+    "y": ((0.0, 1.0, 0.0), (0.0, 0.0, 1.0)),
 }
-AXIS_VIEWS = ("z", "z_back", "x", "y_back")
+AXIS_VIEWS = ("z", "z_back", "x", "y_back", "x_back", "y")   # with these every face of the volume is looked at
 
 # VRC march cases: name -> (sample_distance, front_clip_plane); None = the default 2 / S
 SD_FC = {
@@ -65,6 +69,23 @@ TINY = {
 }
 TINY_VALUES = (0.0, 50.0, 112.0, 150.0, 255.0)   # default TF: class 0, each coloured class, above every interval
 
+# the deep shapes: depth 11, 2048 leaves a side for 9,000 voxels -- the largest LDS carve-up of the shaded
+# march (leaf maps + three raw maps + sample table).  Tiny frame, see deep_cases().
+DEEP = {"deep_x": (1500, 3, 2), "deep_z": (2, 3, 1500)}
+
+# shading coefficient sets (ka, kd, ks, shininess), VR_FLAG_SHADE.  The device evaluates d^shininess
+# with its hardware exp2 / log2, the oracle with exp2f / log2f; everything else of the stage is the
+# same IEEE operations in the same order.  So the frame is the oracle's bit for bit where the specular
+# term is exact: ks = 0 (spec = 0 * finite = +0 and x + 0 = x) and shininess = 0 (spec = ks *
+# exp2(0 * log2 d) = ks).  (1, 0, 0, n) is the identity: k = 1 + 0 * d = 1, rgb * 1 + 0 = rgb.
+SH_KS0 = (0.3, 0.7, 0.0, 16.0)
+SH_N0 = (0.2, 0.5, 0.4, 0.0)
+SH_ID = (1.0, 0.0, 0.0, 7.0)
+SH_GEN = (0.3, 0.7, 0.2, 16.0)
+SH_SHARP = (0.1, 0.6, 0.9, 96.0)
+SHADE_SETS = {"ks0": SH_KS0, "n0": SH_N0, "id": SH_ID, "gen": SH_GEN, "sharp": SH_SHARP}
+SHADE_BITWISE = ("ks0", "n0", "id")
+
 SPECIAL = (np.nan, np.inf, -np.inf, -1.0, -0.0, 255.5, 256.0, 1e30, -1e30, 1e-40, 3.4e38, 127.49999)
 
 
@@ -91,9 +112,28 @@ def blob_special():
     return vol
 
 
+def cube():
+    """(32, 17, 32): integers 0..255, those below 120 zeroed.  x and z fill the octree cube and no face
+    is empty, so the one-sided differences of the shading stage at the six faces are visible."""
+    v = np.random.default_rng(11).integers(0, 256, (32, 17, 32)).astype(F)
+    v[v < 120] = 0
+    return v
+
+
 def tiny_volume(shape):
     """Seeded by the shape (seed word 3: with it the single voxel of (1, 1, 1) draws a coloured class)."""
     return np.random.default_rng([3, *shape]).choice(np.array(TINY_VALUES, F), size=shape).astype(F)
+
+
+def deep_cases(view, **kw):
+    """The frames of a deep shape along a view.  The data is a needle 1500 voxels long and 3 x 2 / 2048
+    of the cube across.  "wide" sees its whole length (axis views only: the oblique rays of a 1.2
+    screen step over it); "narrow" is a 0.02 screen around the centre with 48 samples of 0.002 about
+    it, where every view, obl included, draws (tests/test_param_cases.py)."""
+    centre = float(np.sqrt(np.sum(np.square(VIEWS[view][0]))))
+    narrow = Case(view, VRC, rsw=0.02, sd=0.002, fc=centre - 0.048, frame=(TW, TH, TS), **kw)
+    wide = Case(view, VRC, rsw=1.2, frame=(TW, TH, TS), **kw)
+    return [narrow] if view == "obl" else [wide, narrow]
 
 
 def default_tf():
@@ -112,7 +152,7 @@ class Case:
     """One frame's runtime inputs: the numbers both sides are built from."""
 
     def __init__(self, view, mode=VRC, sd=None, fc=0.0, vpd=2.0, scale=1.0, rsw=RSW, rsh=None, bg=DEFAULT_BG,
-                 conic=False, frame=(W, H, S)):
+                 conic=False, frame=(W, H, S), shade=None):
         self.view, self.mode, self.fc, self.vpd, self.scale = view, mode, float(fc), float(vpd), float(scale)
         self.W, self.H, self.S = frame
         self.sd = 2.0 / self.S if sd is None else float(sd)
@@ -120,10 +160,20 @@ class Case:
         self.rsh = self.rsw * self.H / self.W if rsh is None else float(rsh)
         self.bg = tuple(float(b) for b in bg)
         self.conic = bool(conic)
+        self.shade = None if shade is None else tuple(float(c) for c in shade)   # (ka, kd, ks, shininess)
+        if self.shade is not None and mode != VRC:
+            raise ValueError("shading is defined for VRC only")
+
+    def plain(self):
+        """The same case without shading."""
+        c = Case.__new__(Case)
+        c.__dict__.update(self.__dict__)
+        c.shade = None
+        return c
 
     def key(self):
         return (self.view, self.mode, self.sd, self.fc, self.vpd, self.scale, self.rsw, self.rsh, self.bg,
-                self.conic, self.W, self.H, self.S)
+                self.conic, self.W, self.H, self.S, self.shade)
 
     def pos_up(self):
         pos, up = VIEWS[self.view]
@@ -153,8 +203,10 @@ class Case:
 
     def gpu_params(self, flags=0, ert_epsilon=1e-5):
         import volumerenderingproject_amd as vr
-        p = vr.default_params(self.W, self.H, self.S, mode=self.mode, flags=flags | (CONIC if self.conic else 0),
-                              ert_epsilon=ert_epsilon)
+        flags |= (CONIC if self.conic else 0) | (SHADE if self.shade is not None else 0)
+        p = vr.default_params(self.W, self.H, self.S, mode=self.mode, flags=flags, ert_epsilon=ert_epsilon)
+        if self.shade is not None:
+            p.shade_ambient, p.shade_diffuse, p.shade_specular, p.shade_shininess = self.shade
         p.real_screen_width, p.real_screen_height = self.rsw, self.rsh
         p.viewplane_distance, p.front_clip_plane, p.sample_distance = self.vpd, self.fc, self.sd
         for i in range(4):
@@ -193,7 +245,9 @@ class Reference:
         k = case.key()
         if k not in self._frames:
             p, cam = case.oracle_params(), case.oracle_camera()
-            if case.mode == VRC:
+            if case.shade is not None:
+                f = self.octree.render_vrc_shaded(self.cal, self.otf, p, cam, case.shade)
+            elif case.mode == VRC:
                 f = self.octree.render_vrc(self.cal, self.otf, p, cam)
             elif case.mode == TEST:
                 f = oracle.render_test(self.vol, self.cal, self.otf, p, cam)
@@ -213,7 +267,7 @@ _SHARED = {}
 def shared_reference(name):
     """The Reference of a named volume, one per process: "blob", "avg152", "special" / "special200"
     (blob_special at cal_max 255 / 200.7, closed-form octree), "special_tf0" (blob_special under
-    tf_zero_visible)."""
+    tf_zero_visible), "cube", "deep_x" / "deep_z" (closed-form octree)."""
     if name not in _SHARED:
         if name == "blob":
             _SHARED[name] = Reference(blob(), 255.0)
@@ -223,6 +277,10 @@ def shared_reference(name):
             _SHARED[name] = Reference(blob_special(), 200.7, literal=False)
         elif name == "special_tf0":
             _SHARED[name] = Reference(blob_special(), 255.0, tf=tf_zero_visible(), literal=False)
+        elif name == "cube":
+            _SHARED[name] = Reference(cube(), 255.0)
+        elif name in DEEP:   # (a literal octree of depth 11 is out of reach: closed form)
+            _SHARED[name] = Reference(tiny_volume(DEEP[name]), 255.0, literal=False)
         elif name == "avg152":
             from volumerenderingproject_amd import volumes
             vol, hdr = volumes.avg152()

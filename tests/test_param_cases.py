@@ -100,3 +100,132 @@ def test_zero_visible_tf_tells_nan_from_zero():
             assert np.all(np.isfinite(fa))
             n = int(np.any(fa != fb, axis=-1).sum())
             assert (n >= 5) if differ else (n == 0), (differ, view, n)   # (50 NaN voxels; a few pixels suffice)
+
+
+# ---- the shading stage (VR_FLAG_SHADE): the cases of tests/test_gpu_shade.py are not vacuous ----
+
+SHADE_ROWS = [(v, False) for v in pc.VIEWS] + [("z", True), ("obl", True)]   # (view, conic)
+TINY_SHADED = [(1, 1, 1), (1, 9, 4), (7, 1, 2), (3, 3, 1), (9, 8, 7), (65, 3, 2)]
+
+
+def shade_changes(ref, case, what, expect=True):
+    """The shaded reference differs from the plain one by more than 1e-2 somewhere."""
+    a, b = ref.frame(case), ref.frame(case.plain())
+    assert np.all(np.isfinite(a)), what
+    d = float(np.abs(a.astype(np.float64) - b).max())
+    assert (d > 1e-2) == expect, (what, d)
+
+
+@pytest.mark.parametrize("name", ["blob", "cube"])
+def test_shading_changes_every_view(name):
+    ref = pc.shared_reference(name)
+    for view, conic in SHADE_ROWS:
+        for sname, sh in pc.SHADE_SETS.items():
+            case = Case(view, VRC, conic=conic, shade=sh)
+            check_content(ref.frame(case), (name, view, conic, sname))
+            if sname == "id":   # the identity coefficients: the plain frame bit for bit
+                assert np.array_equal(ref.frame(case).view(np.uint32), ref.frame(case.plain()).view(np.uint32))
+            else:
+                shade_changes(ref, case, (name, view, conic, sname))
+
+
+def test_shaded_reference_follows_conic_and_march_params():
+    """render_vrc_shaded goes through or_vrc_sample_point like the plain march: with the identity
+    coefficients it is the plain frame at every sample distance, front clip and projection, on the
+    literal and on the closed-form octree, and the two octrees agree on a general coefficient set."""
+    ref = pc.shared_reference("blob")
+    closed = pc.Reference(pc.blob(), 255.0, literal=False)
+    rows = [(n, v, False) for n in pc.SD_FC for v in ("z", "x", "obl")] + [(n, v, True) for n in ("default", "fc_in")
+                                                                            for v in ("z", "obl")]
+    for name, view, conic in rows:
+        ident = pc.sd_fc_case(name, view, conic=conic, shade=pc.SH_ID)
+        plain = ref.frame(ident.plain())
+        assert np.array_equal(ref.frame(ident).view(np.uint32), plain.view(np.uint32)), (name, view, conic)
+        case = pc.sd_fc_case(name, view, conic=conic, shade=pc.SH_KS0)
+        shade_changes(ref, case, (name, view, conic))
+        assert np.array_equal(ref.frame(case).view(np.uint32), closed.frame(case).view(np.uint32)), (name, view, conic)
+    # sd, fc and conic are honoured: a shaded frame changes with each of them
+    for view in ("z", "obl"):
+        base = ref.frame(Case(view, VRC, shade=pc.SH_KS0))
+        for other in (pc.sd_fc_case("fc_in", view, shade=pc.SH_KS0), pc.sd_fc_case("sd_big", view, shade=pc.SH_KS0),
+                      Case(view, VRC, conic=True, shade=pc.SH_KS0)):
+            assert int(np.any(ref.frame(other) != base, axis=-1).sum()) >= MIN_PIXELS, (view, other.key())
+
+
+def test_cube_has_a_visible_voxel_in_every_face():
+    ref = pc.shared_reference("cube")
+    v = ref.vol
+    cls = np.array([oracle.tf_class(ref.otf[0], ref.otf[1], float(np.float32(x) / np.float32(255))) for x in range(256)])
+    visible = np.array([ref.tf[k][2][3] != 0.0 for k in cls])[v.astype(int)]
+    for a in range(3):
+        for side in (0, -1):
+            assert visible.take(side, axis=a).any(), (a, side)
+    # and the one-sided difference is not the central one there: some face voxel's gradient changes
+    # when the volume is padded with zeros
+    assert v[0].any() and v[-1].any() and v[:, 0].any() and v[:, -1].any() and v[..., 0].any() and v[..., -1].any()
+
+
+@pytest.mark.parametrize("shape", TINY_SHADED + list(pc.DEEP))
+def test_shaded_small_and_deep_shapes_are_visible(shape):
+    deep = isinstance(shape, str)
+    ref = pc.shared_reference(shape) if deep else pc.Reference(pc.tiny_volume(shape), 255.0)
+    if deep:
+        assert ref.octree.depth == 11 and ref.vol.shape == pc.DEEP[shape]
+    for view in ("z", "x", "obl"):
+        for sh in (pc.SH_KS0, pc.SH_N0):
+            cases = pc.deep_cases(view, shade=sh) if deep else [Case(view, VRC, rsw=pc.TINY[shape],
+                                                                     frame=(pc.TW, pc.TH, pc.TS), shade=sh)]
+            for case in cases:
+                f = ref.frame(case)
+                assert np.all(np.isfinite(f))
+                assert pc.non_background(f) >= 1, (shape, view, case.rsw)
+                if shape != (1, 1, 1):   # (one flat voxel: d = 1, and ka + kd = 1 in SH_KS0)
+                    shade_changes(ref, case, (shape, view, sh, case.rsw))
+
+
+def test_shaded_non_finite_gradients_are_reached():
+    """blob_special under tf_zero_visible: the shaded frame changes when the non-finite voxels are
+    zeroed.  And with NaN and -inf alone zeroed -- voxels that read as 0 either way, so the plain
+    frame stays the same bit for bit -- the shaded frame still changes: that difference can only
+    come from the gradients of their neighbours."""
+    vol = pc.blob_special()
+    a = pc.shared_reference("special_tf0")
+    zeroed = pc.Reference(np.where(np.isfinite(vol), vol, np.float32(0.0)), 255.0, tf=pc.tf_zero_visible(),
+                          literal=False)
+    same_class = pc.Reference(np.where(np.isnan(vol) | (vol == -np.inf), np.float32(0.0), vol), 255.0,
+                              tf=pc.tf_zero_visible(), literal=False)
+    for view in ("z", "obl"):
+        plain = Case(view, VRC)
+        assert np.array_equal(a.frame(plain).view(np.uint32), same_class.frame(plain).view(np.uint32)), view
+        for sh in (pc.SH_KS0, pc.SH_N0):
+            case = Case(view, VRC, shade=sh)
+            fa = a.frame(case)
+            assert np.all(np.isfinite(fa)), (view, sh)
+            for b in (zeroed, same_class):
+                n = int(np.any(fa != b.frame(case), axis=-1).sum())
+                assert n >= 20, (view, sh, n)
+    for name in ("special", "special_tf0"):
+        ref = pc.shared_reference(name)
+        for view in ("z", "obl"):
+            shade_changes(ref, Case(view, VRC, shade=pc.SH_KS0), (name, view))
+
+
+def test_special_volume_holds_a_denormal_headlight_cosine():
+    """blob_special has a voxel whose N.L along z is a positive denormal (its z neighbours are 1e-40
+    and a zero): the device's hardware log2 reads such a d as 0, and d^0 must still be 1 (SH_N0)."""
+    v = pc.blob_special()
+
+    def grad(ax):
+        lo = np.concatenate([np.take(v, [0], ax), np.take(v, range(v.shape[ax] - 1), ax)], ax)
+        hi = np.concatenate([np.take(v, range(1, v.shape[ax]), ax), np.take(v, [-1], ax)], ax)
+        return (hi - lo) * np.float32(0.5)
+
+    with np.errstate(all="ignore"):
+        gx, gy, gz = grad(0), grad(1), grad(2)
+        len2 = (gx * gx + gy * gy) + gz * gz
+        d = -gz * (np.float32(1.0) / np.sqrt(len2))   # view "z": the headlight is (0, 0, 1)
+        tiny = (len2 > 0) & (d > 0) & (d < np.float32(2.0 ** -126)) & (v > 0) & np.isfinite(v)
+    assert int(tiny.sum()) >= 1
+    ref = pc.shared_reference("special")
+    for x in v[tiny]:   # and it is drawn: its class is a visible one
+        assert ref.tf[oracle.tf_class(ref.otf[0], ref.otf[1], float(np.float32(x) / np.float32(255)))][2][3] != 0.0

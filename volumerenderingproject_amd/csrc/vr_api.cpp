@@ -1596,6 +1596,22 @@ void ensure_dvr(vr_ctx* c) {
     }
 }
 
+// Per-voxel normals of VR_FLAG_SHADE, built once per volume by the first shaded frame on the stream
+// that frame runs on.  Inside a batch with frames in flight (frames_in_flight) the other streams were
+// forked before this launch: they wait for it here, or the batch's later frames would read the
+// normals while they are written.
+void ensure_normals(vr_ctx* c, const vr_params* p) {
+    if (!(p->flags & VR_FLAG_SHADE) || c->nrm.p) return;
+    const int64_t n = c->d[0] * c->d[1] * c->d[2];
+    c->nrm.ensure((size_t)n * sizeof(float4));
+    hip_check(launch_normals(c->vol.as<float>(), c->d[0], c->d[1], c->d[2], c->nrm.as<float4>(), c->stream));
+    if (c->batch_main) {
+        hip_check(hipEventRecord(c->fork_ev, c->stream));
+        for (hipStream_t s : {c->batch_main, c->aux_stream[0], c->aux_stream[1], c->aux_stream[2]})
+            if (s && s != c->stream) hip_check(hipStreamWaitEvent(s, c->fork_ev, 0));
+    }
+}
+
 void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const WorkView& wv, float4* out, int out_tiles,
                   int tile_w, int tile_h, int out_rgb, const TileRect* rect, const ColumnSlice* pre) {
     const WorkView* wc = &wv;
@@ -1613,11 +1629,7 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
     }
 
     if (p->mode == VR_MODE_VRC) {
-        if ((p->flags & VR_FLAG_SHADE) && !c->nrm.p) {   // per-voxel normals, built on first shaded frame
-            const int64_t n = c->d[0] * c->d[1] * c->d[2];
-            c->nrm.ensure((size_t)n * sizeof(float4));
-            hip_check(launch_normals(c->vol.as<float>(), c->d[0], c->d[1], c->d[2], c->nrm.as<float4>(), c->stream));
-        }
+        ensure_normals(c, p);
         VrcFrame f = make_vrc_march(c, p, cam);
         f.out_tiles = out_tiles; f.tile_w = tile_w; f.tile_h = tile_h; f.n_work = wc->n_work; f.out_rgb = out_rgb;
         f.n_slots = wc->n_blocks;
