@@ -203,6 +203,13 @@ typedef struct {
                                   copy of the volume when every voxel is an integer in 0..255 (lossless:
                                   four dword gathers per sample), else the float volume; 1 = always the
                                   float volume (eight float gathers).  Bitwise the same frames        */
+    /* render */
+    int32_t column_overlap;    /* vr_render_batch on the column path (axis_columns) with frames in flight:
+                                  1 (default) = only the first two frames' column march comes before
+                                  the frames fork over the in-flight streams; the later marches, six
+                                  frames a launch, are queued on those streams in turn, each beside the
+                                  expand passes of the six frames before.  0 = every march first, then
+                                  the expands.  Launch order only: bitwise the same frames            */
 } vr_options;
 
 int vr_options_default(vr_options* out);

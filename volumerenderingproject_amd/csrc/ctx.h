@@ -173,8 +173,11 @@ struct vr_ctx {
     // axis-aligned views' column path (vr_options.axis_columns): the column buffer of the frame in
     // flight on each stream (float4 per leaf column of its rectangle), per stream like axtab
     std::map<hipStream_t, vr::DevBuf> colbufs;
-    // vr_render_batch: the column buffers of a call's frames back to back (premarch_columns)
+    // vr_render_batch: the column buffers of a call's frames back to back (plan_columns)
     vr::DevBuf colbatch;
+    // vr_options.column_overlap: chunk k's expands wait for col_ev[k & 1], recorded behind its march on
+    // one of the in-flight streams (vr_render_batch)
+    hipEvent_t col_ev[2] = {nullptr, nullptr};
     int occ_lo[3] = {0, 0, 0}, occ_hi[3] = {-1, -1, -1};   // occupied macro-cell range per axis
     // per axis a: summed-area table over the (a0, a1) plane (the other two axes, ascending) of the
     // cell columns along a holding an occupied cell, (ncell + 1)^2 entries (farm-tile cull of

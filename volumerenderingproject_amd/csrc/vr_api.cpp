@@ -551,6 +551,7 @@ void check_options(const vr_options& o) {
     if (o.test_corners < 0 || o.test_corners > 3) throw Error(VR_EINVAL, "vr_options: test_corners must be 0..3");
     if (o.leaf_columns < 0 || o.leaf_columns > 1) throw Error(VR_EINVAL, "vr_options: leaf_columns must be 0 or 1");
     if (o.axis_columns < 0 || o.axis_columns > 2) throw Error(VR_EINVAL, "vr_options: axis_columns must be 0, 1 or 2");
+    if (o.column_overlap < 0 || o.column_overlap > 1) throw Error(VR_EINVAL, "vr_options: column_overlap must be 0 or 1");
     if (o.dvr_volume < 0 || o.dvr_volume > 1) throw Error(VR_EINVAL, "vr_options: dvr_volume must be 0 or 1");
     if (o.farm_tile <= 0 || o.farm_tile % kWgRaysX || o.farm_tile > 4096)
         throw Error(VR_EINVAL, "vr_options: farm_tile must be a positive multiple of 16");
@@ -1719,7 +1720,7 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
 #endif
         ColumnPlan cp;
         if (!pre && rect && !out_tiles && !out_rgb) cp = axis_columns_plan(c, p, f, *rect);
-        if (pre) {   // the frame's columns are marched already (vr_render_batch, premarch_columns): expand only
+        if (pre) {   // the frame's columns are marched already (vr_render_batch, march_columns): expand only
             f.col_i0 = pre->i0; f.col_i1 = pre->i1; f.col_n0 = pre->n0; f.col_n1 = pre->n1;
             hip_check(launch_axis_expand(f, wc->work, n_launch, pre->buf, out, c->stream));
         } else if (cp.take) {
@@ -1877,9 +1878,13 @@ void assemble_slots(vr_ctx* c, int W, int H, int tile_w, int tile_h, const std::
                                    reinterpret_cast<float4*>(d_frame), out_rgb, c->stream));
 }
 
+// vr_options.frames_in_flight: 0 = one stream, k = k + 1 streams (frame f on stream f mod (k + 1))
+static int in_flight_streams(const vr_ctx* c, int n) {
+    return std::min(std::min(n, (int)c->opt.frames_in_flight + 1), 4);
+}
+
 void frames_in_flight(vr_ctx* c, int n, const std::function<void(int)>& launch) {
-    // vr_options.frames_in_flight: 0 = one stream, k = k + 1 streams (frame f on stream f mod (k + 1))
-    const int ns = std::min(std::min(n, (int)c->opt.frames_in_flight + 1), 4);
+    const int ns = in_flight_streams(c, n);
     if (ns <= 1) {
         for (int f = 0; f < n; ++f) launch(f);
         return;
@@ -1945,6 +1950,8 @@ void destroy_ctx_single(vr_ctx* c) {
         if (c->join_ev[i]) (void)hipEventDestroy(c->join_ev[i]);
     }
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
+    for (hipEvent_t e : c->col_ev)
+        if (e) (void)hipEventDestroy(e);
     delete c;
 }
 
@@ -2052,6 +2059,7 @@ int vr_options_default(vr_options* o) {
     o->leaf_columns = 1;   // C3 default view
     o->axis_columns = 1;
     o->dvr_volume = 0;
+    o->column_overlap = 1;
     return VR_OK;
 }
 
@@ -2153,22 +2161,27 @@ int vr_render(vr_ctx* c, const vr_params* p, const vr_camera* cam, float* out, i
 }
 
 // vr_render_batch, column path: the column marches of the call's frames, kColBatch frames to a launch
-// (grid y = frame), on the ctx stream before the frames fork over the in-flight streams; each frame's
-// launch is then its expand pass alone.  A frame's column march is a few hundred workgroups of
-// latency-bound rays -- about as long alone as a whole per-pixel march -- and a second launch per
-// frame costs the host as much as the first: together the marches fill the GPU, at a sixth of a launch
-// per frame.  The frames taken are those in axis_columns_plan's scope that share the first one's
-// kernel variant (view axis, table form); the others keep their own march in launch_frame.
-// pre[i].buf is null for those.  The call's column buffer is reused call after call in stream order
-// (the call's last join puts every expand before the next call's march).
-void premarch_columns(vr_ctx* c, const vr_params* p, const vr_camera* cams, int n, const std::vector<TileRect>& rects,
-                      std::vector<ColumnSlice>& pre) {
+// (grid y = frame); each frame's launch is then its expand pass alone.  A frame's column march is a
+// few hundred workgroups of latency-bound rays -- about as long alone as a whole per-pixel march --
+// and a second launch per frame costs the host as much as the first: together the marches fill the
+// GPU, at a sixth of a launch per frame.  The frames taken are those in axis_columns_plan's scope that
+// share the first one's kernel variant (view axis, table form); the others keep their own march in
+// launch_frame.  pre[i].buf is null for those.  Every frame has its own slice of the call's column
+// buffer, which is reused call after call in stream order (the call's first march follows the last
+// call's joins on the ctx stream, and every other launch of the call follows the fork after it).
+struct ColumnMarches {
+    std::vector<VrcFrame> fcs;   // the frames taken, in call order, and
+    std::vector<int> idx;        //   their indices in the call
+    int grid = 0;
+    std::vector<size_t> chunk;   // launch k marches fcs[chunk[k], chunk[k + 1])
+};
+
+void plan_columns(vr_ctx* c, const vr_params* p, const vr_camera* cams, int n, const std::vector<TileRect>& rects,
+                  ColumnMarches& m, std::vector<ColumnSlice>& pre) {
     pre.assign((size_t)n, ColumnSlice{nullptr, 0, 0, 0, 0});
     if (n < 2 || c->opt.axis_columns == 0 || p->mode != VR_MODE_VRC || c->timing) return;
-    std::vector<VrcFrame> fcs;
-    std::vector<int> idx;
+    std::vector<VrcFrame>& fcs = m.fcs;
     int64_t total = 0;
-    int grid = 0;
     for (int i = 0; i < n; ++i) {
         const VrcFrame f = make_vrc_march(c, p, &cams[i]);
         const ColumnPlan cp = axis_columns_plan(c, p, f, rects[(size_t)i]);
@@ -2177,27 +2190,38 @@ void premarch_columns(vr_ctx* c, const vr_params* p, const vr_camera* cams, int 
         if (!fcs.empty() && (fc.axis1 != fcs[0].axis1 || fc.tsplit != fcs[0].tsplit || fc.zrun != fcs[0].zrun)) continue;
         fc.col_ofs = total;
         total += ((int64_t)cp.n0 * cp.n1 + 15) & ~(int64_t)15;
-        grid = std::max(grid, fc.n_slots);
+        m.grid = std::max(m.grid, fc.n_slots);
         fcs.push_back(fc);
-        idx.push_back(i);
+        m.idx.push_back(i);
     }
-    if (fcs.size() < 2) return;
-    for (VrcFrame& fc : fcs) fc.n_slots = grid;   // (every workgroup of the launch walks its own frame's tiles)
+    if (fcs.size() < 2) {
+        fcs.clear();
+        m.idx.clear();
+        return;
+    }
+    for (VrcFrame& fc : fcs) fc.n_slots = m.grid;   // (every workgroup of the launch walks its own frame's tiles)
     const size_t need = (size_t)total * sizeof(float4);
     if (need > c->colbatch.bytes) {
         if (c->colbatch.p) retire_buffers(c, {&c->colbatch});
         c->colbatch.ensure(need + need / 4);
     }
-    for (size_t k = 0; k < fcs.size(); k += kColBatch)
-        hip_check(launch_vrc_columns(fcs.data() + k, (int)std::min<size_t>(kColBatch, fcs.size() - k), grid,
-                                     c->cls_vrc.as<uint8_t>(), c->pmaps.as<int32_t>(), c->tf_rgba.as<float4>(),
-                                     (int)c->tf.size(), c->colbatch.as<float4>(), c->stream, c->batch,
-                                     (c->leafcols ? c->occ_leafcols : c->occ_cols).as<unsigned long long>(), nullptr,
-                                     nullptr));
     for (size_t k = 0; k < fcs.size(); ++k)
-        pre[(size_t)idx[k]] = ColumnSlice{c->colbatch.as<float4>() + fcs[k].col_ofs, fcs[k].col_i0, fcs[k].col_i1,
-                                          fcs[k].col_n0, fcs[k].col_n1};
+        pre[(size_t)m.idx[k]] = ColumnSlice{c->colbatch.as<float4>() + fcs[k].col_ofs, fcs[k].col_i0, fcs[k].col_i1,
+                                            fcs[k].col_n0, fcs[k].col_n1};
 }
+
+void march_columns(vr_ctx* c, const ColumnMarches& m, size_t k, hipStream_t st) {
+    hip_check(launch_vrc_columns(m.fcs.data() + m.chunk[k], (int)(m.chunk[k + 1] - m.chunk[k]), m.grid,
+                                 c->cls_vrc.as<uint8_t>(), c->pmaps.as<int32_t>(), c->tf_rgba.as<float4>(),
+                                 (int)c->tf.size(), c->colbatch.as<float4>(), st, c->batch,
+                                 (c->leafcols ? c->occ_leafcols : c->occ_cols).as<unsigned long long>(), nullptr,
+                                 nullptr));
+}
+
+// The first launch of a pipelined call (vr_options.column_overlap) marches this many frames: nothing
+// hides it, and a short march is a few us less than a full one; the launches after it, kColBatch frames
+// each, run beside the expands of the chunk before (2 then 6s against a uniform 6).
+constexpr size_t kColFirst = 2;
 
 int vr_render_batch(vr_ctx* c, const vr_params* p, const vr_camera* cams, int32_t n_frames, float* out,
                     int32_t out_flags) {
@@ -2223,8 +2247,39 @@ int vr_render_batch(vr_ctx* c, const vr_params* p, const vr_camera* cams, int32_
         if (c->cull)
             for (int32_t f = 0; f < n_frames; ++f) rects[(size_t)f] = visible_rect(c, p, &cams[f], kWgRaysX, kWgRaysY);
         std::vector<ColumnSlice> pre;
-        premarch_columns(c, p, cams, n_frames, rects, pre);
+        ColumnMarches m;
+        plan_columns(c, p, cams, n_frames, rects, m, pre);
+        // vr_options.column_overlap.  0, or one stream: every march first, on the ctx stream, then the
+        // fork.  1: only the first chunk (kColFirst frames) comes before the fork; chunk k + 1's march
+        // is queued when the host reaches chunk k's first frame, ahead of that chunk's expands, on the
+        // in-flight stream (k + 1) mod ns -- that stream's frames of chunk k wait behind it while the
+        // other streams expand.  Chunk k's expands wait for col_ev[k & 1], recorded behind its march
+        // (and recorded again, for chunk k + 2, only after those waits are queued); on the stream that
+        // marched the chunk, stream order does.  No stream but the in-flight ones, which the call joins.
+        const int ns = in_flight_streams(c, n_frames);
+        const bool overlap = ns > 1 && !m.fcs.empty() && c->opt.column_overlap != 0;
+        for (size_t k = 0; k < m.fcs.size(); k += (overlap && k == 0) ? kColFirst : (size_t)kColBatch) m.chunk.push_back(k);
+        m.chunk.push_back(m.fcs.size());
+        const size_t nchunk = m.chunk.size() - 1;
+        for (size_t k = 0; k < (overlap ? std::min<size_t>(1, nchunk) : nchunk); ++k) march_columns(c, m, k, c->stream);
+        std::vector<int> chunk_of((size_t)n_frames, -1);   // frame -> the chunk it opens
+        if (overlap && nchunk > 1) {
+            for (hipEvent_t& e : c->col_ev)
+                if (!e) hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            for (size_t k = 0; k < nchunk; ++k) chunk_of[(size_t)m.idx[m.chunk[k]]] = (int)k;
+        }
+        auto in_flight = [&](size_t i) { return i % (size_t)ns ? c->aux_stream[i % (size_t)ns - 1] : c->batch_main; };
         frames_in_flight(c, n_frames, [&](int f) {
+            if (chunk_of[(size_t)f] >= 0) {
+                const size_t k = (size_t)chunk_of[(size_t)f];
+                if (k + 1 < nchunk) {
+                    march_columns(c, m, k + 1, in_flight(k + 1));
+                    hip_check(hipEventRecord(c->col_ev[(k + 1) & 1], in_flight(k + 1)));
+                }
+                if (k > 0)
+                    for (size_t i = 0; i < (size_t)ns; ++i)
+                        if (in_flight(i) != in_flight(k)) hip_check(hipStreamWaitEvent(in_flight(i), c->col_ev[k & 1], 0));
+            }
             const TileRect& rect = rects[(size_t)f];
             WorkCache* wc = c->order_mode == 0 ? frame_list(c, p, &cams[f], rect)
                                                : work_for(c, p->width, p->height, 0, 0, 0, 1, nullptr, &rect);

@@ -113,7 +113,8 @@ class Options(C.Structure):
                 ("test_corners", C.c_int32),
                 ("leaf_columns", C.c_int32),
                 ("axis_columns", C.c_int32),
-                ("dvr_volume", C.c_int32)]
+                ("dvr_volume", C.c_int32),
+                ("column_overlap", C.c_int32)]
 
 
 class WorkCount(C.Structure):
