@@ -62,6 +62,20 @@ extern "C" {
                               and > 0 (VR_EINVAL at render); the array the march reads (a byte copy of
                               the volume, else the float volume) must stay below 2^31 bytes (VR_ERANGE).
                               vr_count_samples / vr_count_marched / vr_count_work: VR_EINVAL            */
+#define VR_MODE_MIP 7      /* maximum-intensity projection of the same trilinear field (no reference mode).
+                              VR_MODE_DVR's sample positions, in-volume test and sample value v, operation
+                              for operation; m = the maximum of v over the ray's in-volume samples, from
+                              -inf and replaced only when v > m (a NaN is never taken).  The pixel: without
+                              an in-volume sample the background's r, g, b with alpha 1, otherwise
+                              g = min(max((float)((double)m / cal_max), 0.0f), 1.0f) as (g, g, g, 1).  The
+                              transfer function plays no part (vr_set_transfer_function never changes a
+                              MIP frame).  VR_FLAG_ESS (a ray skips the cells whose upper bound cannot
+                              exceed its running maximum) and VR_FLAG_ERT (it stops once nothing in the
+                              volume can) are accepted and change no value: the four combinations give
+                              the same frame bit for bit.  VR_FLAG_SHADE / VR_FLAG_CONIC are VR_EINVAL;
+                              cal_max must be finite and > 0 (VR_EINVAL at render); the size limit is
+                              VR_MODE_DVR's (VR_ERANGE).  vr_count_samples / vr_count_marched /
+                              vr_count_work: VR_EINVAL; vr_axis_columns_plan reports no column path      */
 
 /* ---- render flags -------------------------------------------------------------------------- */
 #define VR_FLAG_ESS 1      /* empty-space skipping (bitwise exact: skips only alpha-0 samples)  */
@@ -98,9 +112,10 @@ typedef struct {
 
 /* AppData render fields (utils.h:36-74) made runtime.  vr_params_default fills the reference's
  * values for a given W, H, S.  Every finite value is defined: a zero or negative sample_distance
- * (VRC: S copies of one point / the march runs backwards) and viewplane_distance (TEST, DVR) render
+ * (VRC: S copies of one point / the march runs backwards) and viewplane_distance (TEST, DVR, MIP) render
  * the reference's arithmetic as written.  background[3] is ignored: a frame's alpha is 1
- * (kernel.cu:213).  VRC normalises by (float)(int)cal_max, TEST and DVR by the double cal_max. */
+ * (kernel.cu:213).  VRC normalises by (float)(int)cal_max, TEST, DVR and MIP by the double
+ * cal_max. */
 typedef struct {
     int32_t width, height, samples_per_ray, mode, flags;
     float real_screen_width, real_screen_height, viewplane_distance, front_clip_plane,

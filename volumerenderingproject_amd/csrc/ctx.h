@@ -202,6 +202,11 @@ struct vr_ctx {
     bool dvr_cells_valid = false, dvr_tf_valid = false;
     int dvr_tcb = 3, dvr_tnc[3] = {0, 0, 0};
     vr::DvrFrame dvr_frame{};                // nseg, seg0 and the SGPR starts of the current TF
+    // VR_MODE_MIP (vr_mip.hip), built on the first MIP frame beside dvr_u8 / dvr_minmax (which either
+    // mode builds first): one float per cell, an upper bound of every sample based in it, and their maximum
+    vr::DevBuf mip_bound;
+    bool mip_valid = false;
+    float mip_vol_bound = 0.0f;
     // TEST: a voxel on the volume's faces is not class 0 (test_faces_kernel; 1 until classified)
     vr::DevBuf faces_flag;
     int32_t test_faces_dirty = 1;

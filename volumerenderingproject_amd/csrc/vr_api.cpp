@@ -6,6 +6,7 @@
 //   cls_vrc    uint8 class per voxel for VRC      (TF of max(0,v)/(float)(int)cal_max)
 //   cls_test   uint8 class per voxel for TEST     (TF of (float)(v/cal_max)), built on first use
 //   dvr_*      VR_MODE_DVR: byte copy of the volume, cell min/max and bits, TF segments, built on first use
+//   mip_bound  VR_MODE_MIP: the cells' upper bounds (with DVR's byte copy and cell min/max), built on first use
 //   maps       3 x 2^D int32 leaf -> voxel maps (the octree leaf grid in closed form)
 //   occ        macro-cell occupancy bitmask over the leaf grid (ESS)
 //   tf_rgba    class colours; tf_lohi interval bounds
@@ -69,6 +70,9 @@ size_t dvr_lds_bytes(const TestFrame&, const DvrFrame&, bool);
 hipError_t launch_dvr_bytes(const float*, int64_t, uint8_t*, int32_t*, hipStream_t);
 hipError_t launch_dvr_minmax(const float*, int64_t, int64_t, int64_t, int, int, int, int, float2*, hipStream_t);
 hipError_t launch_dvr_cells(const float2*, int64_t, const float*, const float4*, int, unsigned long long*, hipStream_t);
+hipError_t launch_mip_march(const TestFrame&, const MipFrame&, const WorkTile*, int, const void*, bool, const float*,
+                            float4*, hipStream_t);
+hipError_t launch_mip_bounds(const float2*, int64_t, float*, hipStream_t);
 hipError_t launch_assemble(int, int, int, int, int, int, const float4*, float4*, int, hipStream_t);
 hipError_t launch_assemble_list(int, int, int, int, const int32_t*, const float4*, float4, float4*, int, hipStream_t,
                                 int n_frames = 1);
@@ -796,8 +800,8 @@ WorkCache* frame_list(vr_ctx* c, const vr_params* p, const vr_camera* cam, const
 #ifndef VR_TEST_AXIS_COLUMN_DEAL
 #define VR_TEST_AXIS_COLUMN_DEAL 0
 #endif
-    // (DVR frames: one general march for every view, its volume read like the corner volume)
-    const int deal = (p->mode == VR_MODE_DVR ||
+    // (DVR and MIP frames: one general march for every view, its volume read like the corner volume)
+    const int deal = (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP ||
                       (p->mode == VR_MODE_TEST && (VR_TEST_AXIS_COLUMN_DEAL || make_test(c, p, cam).axt < 0))) ? 1 : 0;
     std::vector<uint32_t> key = {(uint32_t)W, (uint32_t)H, (uint32_t)tx0, (uint32_t)tx1, (uint32_t)ty0, (uint32_t)ty1,
                                  (uint32_t)ma, (uint32_t)deal};
@@ -853,8 +857,9 @@ int hull_edges(const vr_ctx* c, const vr_params* p, const vr_camera* cam, float 
 // nothing can be visible, 2 when no claim can be made (TEST mode, opaque TF(0), a corner behind a
 // conic camera, a NaN camera), 1 with the points in xy.
 int project_box(const vr_ctx* c, const vr_params* p, const vr_camera* cam, double xy[8][2]) {
-    // (DVR: TEST's positions and in-volume test, TF(0) outside)
-    if (p->mode == VR_MODE_TEST || p->mode == VR_MODE_DVR) return project_box_test(c, p, cam, xy);
+    // (DVR, MIP: TEST's positions and in-volume test)
+    if (p->mode == VR_MODE_TEST || p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP)
+        return project_box_test(c, p, cam, xy);
     if (p->mode != VR_MODE_VRC || !c->zero_transparent) return 2;
     double lo[3], hi[3];
     for (int a = 0; a < 3; ++a) {
@@ -895,8 +900,9 @@ int project_box(const vr_ctx* c, const vr_params* p, const vr_camera* cam, doubl
 // transparent an exact no-op of either blend.  So a ray whose line misses the dataset box [0, d]^3
 // is exactly the background: the box's 8 corners mapped back to (x, y) through M^-1 (double
 // precision; the float matrices' rounding is far inside the 2-pixel margin visible_rect adds).
+// MIP frames: a ray without an in-volume sample is the background by definition, whatever TF(0) is.
 int project_box_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam, double xy[8][2]) {
-    if (!c->zero_transparent) return 2;
+    if (!c->zero_transparent && p->mode != VR_MODE_MIP) return 2;
     CameraState cs;
     cs.pos = {cam->pos[0], cam->pos[1], cam->pos[2]};
     cs.up = {cam->up[0], cam->up[1], cam->up[2]};
@@ -1148,7 +1154,7 @@ std::vector<int32_t> visible_tiles_uncached(const vr_ctx* c, const vr_params* p,
 void check_params(const vr_params* p) {
     if (!p || p->width <= 0 || p->height <= 0 || p->samples_per_ray <= 0 || p->width > 65535 || p->height > 65535)
         throw Error(VR_EINVAL, "vr_params: bad width/height/samples_per_ray");
-    if (p->mode != VR_MODE_VRC && p->mode != VR_MODE_TEST && p->mode != VR_MODE_DVR)
+    if (p->mode != VR_MODE_VRC && p->mode != VR_MODE_TEST && p->mode != VR_MODE_DVR && p->mode != VR_MODE_MIP)
         throw Error(VR_EINVAL, "vr_params: unknown mode");
     if (p->flags & ~(VR_FLAG_ESS | VR_FLAG_ERT | VR_FLAG_SHADE | VR_FLAG_CONIC))
         throw Error(VR_EINVAL, "vr_params: unknown flags");
@@ -1319,7 +1325,8 @@ TestFrame make_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam) {
     f.d1 = c->d[0]; f.d2 = c->d[1]; f.d3 = c->d[2];
     f.total = c->d[0] * c->d[1] * c->d[2];
     f.fd1 = (float)c->d[0]; f.fd2 = (float)c->d[1]; f.fd3 = (float)c->d[2];
-    f.zero_transparent = c->zero_transparent ? 1 : 0;
+    // (MIP: samples outside the volume take no part, so the clip and the culls hold for any TF)
+    f.zero_transparent = (c->zero_transparent || p->mode == VR_MODE_MIP) ? 1 : 0;
     f.cls0 = c->cls0_test;
     f.idx64 = (f.total + f.d2 * f.d3 + f.d3 + 1) >= ((int64_t)1 << 31) ? 1 : 0;
     f.tcb = c->tcb;
@@ -1524,13 +1531,13 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, WorkCache
     launch_frame(c, p, cam, wv, out, out_tiles, tile_w, tile_h, out_rgb, rect, pre);
 }
 
-// VR_MODE_DVR's lazy state, on c->stream: the byte copy of the volume (first frame; kept only when
-// lossless), the cells' min/max (first frame) and -- whenever the TF changed -- the TF's segments and
-// the cells' occupancy bits.  Throws VR_EINVAL for a cal_max the mode is not defined for and
-// VR_ERANGE for a volume past 32-bit byte offsets.
-void ensure_dvr(vr_ctx* c) {
+// The lazy state VR_MODE_DVR and VR_MODE_MIP share, on c->stream, built by the first frame of either:
+// the byte copy of the volume (kept only when lossless) and the cells' min/max.  Nothing here follows
+// the TF.  Throws VR_EINVAL for a cal_max the modes are not defined for and VR_ERANGE for a volume
+// past 32-bit byte offsets.
+void ensure_dvr_volume(vr_ctx* c) {
     if (!(c->cal_max > 0.0) || !std::isfinite(c->cal_max))
-        throw Error(VR_EINVAL, "VR_MODE_DVR: cal_max must be finite and > 0");
+        throw Error(VR_EINVAL, "VR_MODE_DVR / VR_MODE_MIP: cal_max must be finite and > 0");
     const int64_t n = c->d[0] * c->d[1] * c->d[2];
     const int64_t lim = ((int64_t)1 << 31) - 1;
     if (c->dvr_u8_state == 0) {
@@ -1549,7 +1556,8 @@ void ensure_dvr(vr_ctx* c) {
             else c->dvr_u8.reset();
         }
     }
-    if (c->dvr_u8_state != 1 && n * 4 > lim) throw Error(VR_ERANGE, "VR_MODE_DVR: volume too large for 32-bit offsets");
+    if (c->dvr_u8_state != 1 && n * 4 > lim)
+        throw Error(VR_ERANGE, "VR_MODE_DVR / VR_MODE_MIP: volume too large for 32-bit offsets");
     if (!c->dvr_cells_valid) {   // cells of 8^3 voxels, coarser until the bitmask is <= 2^18 bits
         c->dvr_tcb = 3;
         auto nc = [&](int a) { return (int)((c->d[a] + (1 << c->dvr_tcb) - 1) >> c->dvr_tcb); };
@@ -1557,13 +1565,18 @@ void ensure_dvr(vr_ctx* c) {
         for (int a = 0; a < 3; ++a) c->dvr_tnc[a] = nc(a);
         const int64_t cells = (int64_t)c->dvr_tnc[0] * c->dvr_tnc[1] * c->dvr_tnc[2];
         c->dvr_minmax.ensure((size_t)cells * sizeof(float2));
-        c->dvr_occ.ensure((size_t)((cells + 63) / 64) * 8);
         hip_check(launch_dvr_minmax(c->vol.as<float>(), c->d[0], c->d[1], c->d[2], c->dvr_tcb, c->dvr_tnc[0],
                                     c->dvr_tnc[1], c->dvr_tnc[2], c->dvr_minmax.as<float2>(), c->stream));
         group_mark(c);
         c->dvr_cells_valid = true;
         c->dvr_tf_valid = false;
     }
+}
+
+// VR_MODE_DVR's lazy state: ensure_dvr_volume and -- whenever the TF changed -- the TF's segments and
+// the cells' occupancy bits.
+void ensure_dvr(vr_ctx* c) {
+    ensure_dvr_volume(c);
     if (!c->dvr_tf_valid) {
         const std::vector<TransferFunction::Segment> seg = tf_segments(c->tf.data(), (int)c->tf.size(), c->cal_max);
         const int nseg = (int)seg.size();
@@ -1583,6 +1596,7 @@ void ensure_dvr(vr_ctx* c) {
         ctx_sync(c, c->stream);   // (queued launches read the old tables)
         c->dvr_start.ensure((size_t)kMaxDvrSeg * sizeof(float));
         c->dvr_seg.ensure((size_t)kMaxDvrSeg * sizeof(float4));
+        c->dvr_occ.ensure((size_t)(((int64_t)c->dvr_tnc[0] * c->dvr_tnc[1] * c->dvr_tnc[2] + 63) / 64) * 8);
         hip_check(hipMemcpyAsync(c->dvr_start.p, starts.data(), starts.size() * sizeof(float), hipMemcpyHostToDevice,
                                  c->stream));
         hip_check(hipMemcpyAsync(c->dvr_seg.p, rgba.data(), rgba.size() * sizeof(float4), hipMemcpyHostToDevice,
@@ -1595,6 +1609,23 @@ void ensure_dvr(vr_ctx* c) {
         c->dvr_frame = g;
         c->dvr_tf_valid = true;
     }
+}
+
+// VR_MODE_MIP's lazy state: ensure_dvr_volume and, on the first MIP frame, the cells' upper bounds
+// (mip_bounds_kernel) with their maximum, the volume-wide bound of the ERT stop.  No TF table, no
+// cell bits.  (Host-synchronised like ensure_dvr: a batch's other streams launch after it.)
+void ensure_mip(vr_ctx* c) {
+    ensure_dvr_volume(c);
+    if (c->mip_valid) return;
+    const int64_t cells = (int64_t)c->dvr_tnc[0] * c->dvr_tnc[1] * c->dvr_tnc[2];
+    c->mip_bound.ensure((size_t)cells * sizeof(float));
+    hip_check(launch_mip_bounds(c->dvr_minmax.as<float2>(), cells, c->mip_bound.as<float>(), c->stream));
+    group_mark(c);
+    std::vector<float> h((size_t)cells);
+    hip_check(hipMemcpyAsync(h.data(), c->mip_bound.p, h.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    ctx_sync(c, c->stream);
+    c->mip_vol_bound = *std::max_element(h.begin(), h.end());
+    c->mip_valid = true;
 }
 
 // Per-voxel normals of VR_FLAG_SHADE, built once per volume by the first shaded frame on the stream
@@ -1751,8 +1782,9 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
                                    c->cdist_p, gtab, gtab_out, c->count_ptr));
         if (gtab_out) c->axtab[c->stream].key = std::move(pub_key);   // valid for later launches on this stream
     } else {
-        const bool dvr = p->mode == VR_MODE_DVR;
+        const bool dvr = p->mode == VR_MODE_DVR, mip = p->mode == VR_MODE_MIP;
         if (dvr) ensure_dvr(c);
+        else if (mip) ensure_mip(c);
         else if (!c->cls_test_valid) classify(c, true);
         TestFrame f = make_test(c, p, cam);
         f.out_tiles = out_tiles; f.tile_w = tile_w; f.tile_h = tile_h; f.n_work = wc->n_work; f.out_rgb = out_rgb;
@@ -1784,6 +1816,21 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             if (dvr_lds_bytes(f, g, ess) > (size_t)kDvrLdsMax) f.occ_lds = 0;
             hip_check(launch_dvr_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8, c->dvr_start.as<float>(),
                                        c->dvr_seg.as<float4>(), c->dvr_occ.as<uint32_t>(), out, c->stream));
+        } else if (mip) {
+            // the MIP march: TEST's frame with DVR's cells, plus the cells' bounds (ensure_mip)
+            const int64_t n = c->d[0] * c->d[1] * c->d[2];
+            const bool u8 = c->dvr_u8_state == 1;
+            f.axt = -1;
+            f.tcb = c->dvr_tcb;
+            for (int a = 0; a < 3; ++a) f.tnc[a] = c->dvr_tnc[a];
+            MipFrame g;
+            std::memset(&g, 0, sizeof g);
+            g.cal_max = c->cal_max;
+            g.vol_bound = c->mip_vol_bound;
+            g.vol_bytes = (int32_t)(u8 ? n + 16 : n * 4);   // (the byte copy: a dword at the last voxel stays inside)
+            g.bound_bytes = (int32_t)((int64_t)f.tnc[0] * f.tnc[1] * f.tnc[2] * 4);   // (<= 2^18 cells)
+            hip_check(launch_mip_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8,
+                                       c->mip_bound.as<float>(), out, c->stream));
         } else {
         // axis views: the march axis's tables built here once per view and staged by every workgroup
         // (per stream, like the VRC view tables; a new view first drains the launches of this stream)
@@ -1934,7 +1981,7 @@ void destroy_ctx_single(vr_ctx* c) {
     for (DevBuf* b : {&c->vol, &c->cls_vrc, &c->cls8, &c->cls_gen, &c->layout_gen, &c->pmaps_gen, &c->pmaps_pad, &c->pmaps_gen_pad, &c->cls_test, &c->maps, &c->pmaps, &c->pmapx64, &c->occ, &c->tf_rgba,
                       &c->tf_lohi, &c->alpha_nz, &c->frame, &c->counter, &c->layout, &c->egress, &c->occ_test,
                       &c->occ_cols, &c->occ_leafcols, &c->cdist, &c->nrm, &c->tcol, &c->tcc, &c->tcc_lay, &c->faces_flag,
-                      &c->dvr_u8, &c->dvr_minmax, &c->dvr_occ, &c->dvr_start, &c->dvr_seg})
+                      &c->dvr_u8, &c->dvr_minmax, &c->dvr_occ, &c->dvr_start, &c->dvr_seg, &c->mip_bound})
         b->reset();
     c->work_cache.clear();
     c->slot_maps.clear();
@@ -2453,7 +2500,7 @@ int vr_assemble_tiles(vr_ctx* c, int32_t W, int32_t H, int32_t tile_w, int32_t t
 
 int vr_count_samples(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64_t* n_in) {
     if (!c || !cam || !n_in) return VR_EINVAL;
-    if (p && p->mode == VR_MODE_DVR) return VR_EINVAL;   // (the counting passes cover VRC and TEST)
+    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP)) return VR_EINVAL;   // (the counting passes cover VRC and TEST)
     return guard([&] {
         check_params(p);
         set_device(c);
@@ -2477,7 +2524,8 @@ int vr_count_samples(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64
 // axis_columns_plan's scope), and the tests that pin these counts pin that definition.
 int vr_count_work(vr_ctx* c, const vr_params* p, const vr_camera* cam, vr_work_count* out) {
     if (!c || !cam || !out) return VR_EINVAL;
-    if (p && p->mode == VR_MODE_DVR) return VR_EINVAL;   // (no counting instantiation of the DVR march)
+    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP))
+        return VR_EINVAL;   // (no counting instantiation of the DVR and MIP marches)
     return guard([&] {
         check_params(p);
         set_device(c);
@@ -2773,7 +2821,7 @@ int vr_get_volume_info(vr_ctx* c, vr_volume_info* out) {
     uint64_t b = 0;
     for (DevBuf* d : {&c->vol, &c->cls_vrc, &c->cls8, &c->cls_gen, &c->layout_gen, &c->pmaps_gen, &c->pmaps_pad, &c->pmaps_gen_pad, &c->cls_test, &c->maps, &c->pmaps, &c->pmapx64, &c->occ, &c->tf_rgba,
                       &c->tf_lohi, &c->alpha_nz, &c->frame, &c->counter, &c->layout, &c->egress, &c->occ_test, &c->occ_cols, &c->occ_leafcols, &c->cdist, &c->nrm, &c->tcol, &c->tcc, &c->tcc_lay,
-                      &c->dvr_u8, &c->dvr_minmax, &c->dvr_occ, &c->dvr_start, &c->dvr_seg})
+                      &c->dvr_u8, &c->dvr_minmax, &c->dvr_occ, &c->dvr_start, &c->dvr_seg, &c->mip_bound})
         b += d->bytes;
     out->device_bytes = b;
     out->idx64 = c->idx64 ? 1 : 0;

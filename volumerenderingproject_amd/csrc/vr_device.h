@@ -177,6 +177,16 @@ struct DvrFrame {
     float start[kDvrSeg8];      // nseg <= 9: start[1 .. nseg), the rest NaN (no value is >= NaN)
 };
 
+// The MIP march (vr_mip.hip) takes the same from a TestFrame (zero_transparent = 1: a sample outside
+// the volume takes no part whatever the TF is; tcb / tnc describing the min/max cells) and adds:
+struct MipFrame {
+    double cal_max;             // the pixel is (float)((double)max / cal_max), clamped to [0, 1]
+    float vol_bound;            // the largest cell bound: no sample exceeds it (the ERT stop)
+    int32_t vol_bytes;          // bytes of the array the corner gathers read (their buffer bound)
+    int32_t bound_bytes;        // bytes of the cells' upper bounds (one float per cell)
+    int32_t reserved;
+};
+
 // TransferFunction::getMaterial (TransferFunction.cu:46-55): last closed interval containing v, else 0
 __device__ __forceinline__ int tf_class(const float* lo, const float* hi, int n, float v) {
     int r = 0;

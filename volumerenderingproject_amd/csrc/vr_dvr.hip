@@ -14,14 +14,6 @@
 
 namespace vr {
 
-// a * (1 - w) + b * w on the scalar field, every product and sum rounded on its own.  Classification
-// is discontinuous, so -- unlike TEST's colour lerps -- this is never fused or reassociated, front to
-// back (ERT) included: a one-ulp change of the value could flip a sample's class at a TF boundary.
-__device__ __forceinline__ float lerp1(float a, float b, float w) {
-    const float u = 1.0f - w;
-    return a * u + b * w;
-}
-
 // ------------------------------------------------------------------------------------------------
 // DVR march, one launch per frame, the shape of test_march_kernel: 16 x 16 rays per workgroup (a
 // wave = 8 x 8), work list / background workgroups / hull cull (test_background), TEST's position

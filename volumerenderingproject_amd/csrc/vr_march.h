@@ -1,5 +1,5 @@
 // vr_march.h -- device helpers shared by the march kernels (vr_kernels.hip: VRC and the setup
-// kernels; vr_test.hip: TEST; vr_dvr.hip: DVR).  Internal, not the ABI.
+// kernels; vr_test.hip: TEST; vr_dvr.hip: DVR; vr_mip.hip: MIP).  Internal, not the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -264,7 +264,17 @@ __device__ __forceinline__ void test_cell_jump(const TestFrame& f, const int cc[
     }
 }
 
-// Whole TEST and DVR frames: work tiles off the dataset box's projection (vr_api.cpp project_box_test) are
+// a * (1 - w) + b * w on the scalar field (the DVR and MIP marches), every product and sum rounded on
+// its own.  Classification is discontinuous, so -- unlike TEST's colour lerps -- this is never fused
+// or reassociated, front to back (ERT) included: a one-ulp change of the value could flip a sample's
+// class at a TF boundary (DVR) or pass a cell's upper bound (MIP).
+__device__ __forceinline__ float lerp1(float a, float b, float w) {
+#pragma clang fp contract(off)
+    const float u = 1.0f - w;
+    return a * u + b * w;
+}
+
+// Whole TEST, DVR and MIP frames: work tiles off the dataset box's projection (vr_api.cpp project_box_test) are
 // exactly the background; a background-only workgroup (blockIdx >= bg_first) stores bg_group of
 // them, and a culled tile (slot < 0) among the marching ones stores its own -- both before any
 // staging.  True if this workgroup is done.  (vr_test.hip, vr_dvr.hip)

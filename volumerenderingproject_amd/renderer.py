@@ -22,6 +22,7 @@ VR_OK = 0
 VR_MODE_VRC = 1
 VR_MODE_TEST = 5
 VR_MODE_DVR = 6       # trilinear sample of the scalar field, then TF classification
+VR_MODE_MIP = 7       # maximum-intensity projection of the same trilinear field (no TF)
 VR_FLAG_ESS = 1
 VR_FLAG_ERT = 2
 VR_FLAG_SHADE = 8
