@@ -220,11 +220,12 @@ typedef struct {
                                   float volume (eight float gathers).  Bitwise the same frames        */
     /* render */
     int32_t column_overlap;    /* vr_render_batch on the column path (axis_columns) with frames in flight:
-                                  1 (default) = only the first two frames' column march comes before
-                                  the frames fork over the in-flight streams; the later marches, six
-                                  frames a launch, are queued on those streams in turn, each beside the
-                                  expand passes of the six frames before.  0 = every march first, then
-                                  the expands.  Launch order only: bitwise the same frames            */
+                                  1 (default) = only the first three frames' column march comes before
+                                  the frames fork over the in-flight streams; the later marches, each
+                                  of three times as many frames as the one before (up to 32), are
+                                  queued on those streams in turn, each beside the expand passes of
+                                  the frames of the launch before.  0 = every march first, then the
+                                  expands.  Launch order only: bitwise the same frames                */
 } vr_options;
 
 int vr_options_default(vr_options* out);

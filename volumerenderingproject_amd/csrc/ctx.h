@@ -178,6 +178,21 @@ struct vr_ctx {
     // vr_options.column_overlap: chunk k's expands wait for col_ev[k & 1], recorded behind its march on
     // one of the in-flight streams (vr_render_batch)
     hipEvent_t col_ev[2] = {nullptr, nullptr};
+    // vr_render_batch: the column frames of a call past its first launch, which the later marches read
+    // from device memory (vrc_march_kernel, DEVF).  One upload per call, from the next of a ring of
+    // pinned host slots; a slot's event is recorded behind its copy, and the host waits for it before
+    // writing the slot again (kColStage calls later: as a rule complete long since)
+    // The ring is one pinned allocation of kColStage slots of col_stage_cap frames each, made -- with
+    // the device array, both for at least kColStageMin frames -- by the first call that uploads, so that
+    // no later call of an ordinary size allocates anything.
+    vr::DevBuf colframes;
+    static constexpr int kColStage = 4;
+    static constexpr size_t kColStageMin = 32;
+    vr::VrcFrame* col_stage = nullptr;
+    size_t col_stage_cap = 0;                                            // frames per slot
+    hipEvent_t col_stage_ev[kColStage] = {nullptr, nullptr, nullptr, nullptr};   // behind the last copy out of the slot
+    bool col_stage_used[kColStage] = {false, false, false, false};
+    unsigned col_stage_next = 0;
     int occ_lo[3] = {0, 0, 0}, occ_hi[3] = {-1, -1, -1};   // occupied macro-cell range per axis
     // per axis a: summed-area table over the (a0, a1) plane (the other two axes, ascending) of the
     // cell columns along a holding an occupied cell, (ncell + 1)^2 entries (farm-tile cull of

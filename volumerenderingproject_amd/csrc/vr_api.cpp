@@ -41,7 +41,8 @@ hipError_t launch_vrc_march(const VrcFrame&, const WorkTile*, const int32_t*, in
                             hipStream_t, int, const float*, const int32_t*, const unsigned long long*,
                             const uint8_t*, const int32_t*, int32_t*, unsigned long long*);
 hipError_t launch_vrc_columns(const VrcFrame*, int, int, const uint8_t*, const int32_t*, const float4*, int, float4*,
-                              hipStream_t, int, const unsigned long long*, const int32_t*, int32_t*);
+                              hipStream_t, int, const unsigned long long*, const int32_t*, int32_t*,
+                              const VrcFrame* dev_frames = nullptr);
 hipError_t launch_axis_expand(const VrcFrame&, const WorkTile*, int, const float4*, float4*, hipStream_t);
 size_t vrc_axis1_table_bytes(const VrcFrame&, int);
 int vrc_batch_of(const VrcFrame&, int);
@@ -1989,6 +1990,10 @@ void destroy_ctx_single(vr_ctx* c) {
     c->ztabs.clear();
     c->colbufs.clear();
     c->colbatch.reset();
+    c->colframes.reset();
+    if (c->col_stage) (void)hipHostFree(c->col_stage);   // (the streams are drained: no copy reads a slot any more)
+    for (hipEvent_t e : c->col_stage_ev)
+        if (e) (void)hipEventDestroy(e);
     for (auto* v : {&c->ev_free, &c->ev_pending})
         for (auto& ev : *v) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -2207,11 +2212,11 @@ int vr_render(vr_ctx* c, const vr_params* p, const vr_camera* cam, float* out, i
     });
 }
 
-// vr_render_batch, column path: the column marches of the call's frames, kColBatch frames to a launch
-// (grid y = frame); each frame's launch is then its expand pass alone.  A frame's column march is a
-// few hundred workgroups of latency-bound rays -- about as long alone as a whole per-pixel march --
-// and a second launch per frame costs the host as much as the first: together the marches fill the
-// GPU, at a sixth of a launch per frame.  The frames taken are those in axis_columns_plan's scope that
+// vr_render_batch, column path: the column marches of the call's frames, many frames to a launch
+// (grid y = frame; chunk_columns); each frame's launch is then its expand pass alone.  A frame's column
+// march is a few hundred workgroups of latency-bound rays -- about as long alone as a whole per-pixel
+// march -- and a second launch per frame costs the host as much as the first: together the marches
+// fill the GPU, at a fraction of a launch per frame.  The frames taken are those in axis_columns_plan's scope that
 // share the first one's kernel variant (view axis, table form); the others keep their own march in
 // launch_frame.  pre[i].buf is null for those.  Every frame has its own slice of the call's column
 // buffer, which is reused call after call in stream order (the call's first march follows the last
@@ -2221,6 +2226,9 @@ struct ColumnMarches {
     std::vector<int> idx;        //   their indices in the call
     int grid = 0;
     std::vector<size_t> chunk;   // launch k marches fcs[chunk[k], chunk[k + 1])
+    size_t dev_chunk = 0;        // launches from this one on read their frames from c->colframes (upload_columns):
+    hipStream_t up_st = nullptr; //   uploaded on this stream,
+    hipEvent_t up_ev = nullptr;  //   this event behind the copy
 };
 
 void plan_columns(vr_ctx* c, const vr_params* p, const vr_camera* cams, int n, const std::vector<TileRect>& rects,
@@ -2257,18 +2265,100 @@ void plan_columns(vr_ctx* c, const vr_params* p, const vr_camera* cams, int n, c
                                             fcs[k].col_n0, fcs[k].col_n1};
 }
 
+// Launch k of the call's marches on st.  A launch that reads its frames from device memory
+// (k >= m.dev_chunk) follows their upload: in stream order on the stream that carries it, behind the
+// staging slot's event on any other.
 void march_columns(vr_ctx* c, const ColumnMarches& m, size_t k, hipStream_t st) {
+    const VrcFrame* dev = nullptr;
+    if (k >= m.dev_chunk) {
+        dev = c->colframes.as<VrcFrame>() + (m.chunk[k] - m.chunk[m.dev_chunk]);
+        if (st != m.up_st) hip_check(hipStreamWaitEvent(st, m.up_ev, 0));
+    }
     hip_check(launch_vrc_columns(m.fcs.data() + m.chunk[k], (int)(m.chunk[k + 1] - m.chunk[k]), m.grid,
                                  c->cls_vrc.as<uint8_t>(), c->pmaps.as<int32_t>(), c->tf_rgba.as<float4>(),
                                  (int)c->tf.size(), c->colbatch.as<float4>(), st, c->batch,
                                  (c->leafcols ? c->occ_leafcols : c->occ_cols).as<unsigned long long>(), nullptr,
-                                 nullptr));
+                                 nullptr, dev));
 }
 
-// The first launch of a pipelined call (vr_options.column_overlap) marches this many frames: nothing
-// hides it, and a short march is a few us less than a full one; the launches after it, kColBatch frames
-// each, run beside the expands of the chunk before (2 then 6s against a uniform 6).
-constexpr size_t kColFirst = 2;
+// The one upload of a call: the frames of the launches from m.dev_chunk on, through the next pinned
+// staging slot into c->colframes, on st ahead of the first march that reads them.  One device buffer
+// serves every call: st is the ctx stream, or an in-flight stream that waits on this call's fork from
+// it, and every march of the calls before was joined into the ctx stream (the argument above
+// ColumnMarches) -- the copy overwrites nothing a queued march still reads.  The buffer grows like
+// colbatch, the old one retired behind the work queued so far.
+void upload_columns(vr_ctx* c, ColumnMarches& m, hipStream_t st) {
+    const size_t b = m.chunk[m.dev_chunk], n = m.fcs.size() - b;
+    if (n * sizeof(VrcFrame) > c->colframes.bytes) {
+        if (c->colframes.p) retire_buffers(c, {&c->colframes});
+        c->colframes.ensure(std::max(vr_ctx::kColStageMin, 2 * n) * sizeof(VrcFrame));
+    }
+    if (n > c->col_stage_cap) {   // a new ring, once every copy out of the old one is complete
+        for (int i = 0; i < vr_ctx::kColStage; ++i) {
+            if (c->col_stage_used[i]) hip_check(hipEventSynchronize(c->col_stage_ev[i]));
+            c->col_stage_used[i] = false;
+            if (!c->col_stage_ev[i]) hip_check(hipEventCreateWithFlags(&c->col_stage_ev[i], hipEventDisableTiming));
+        }
+        if (c->col_stage) (void)hipHostFree(c->col_stage);
+        c->col_stage = nullptr;
+        c->col_stage_cap = 0;
+        const size_t cap = std::max(vr_ctx::kColStageMin, 2 * n);
+        hip_check(hipHostMalloc(reinterpret_cast<void**>(&c->col_stage), vr_ctx::kColStage * cap * sizeof(VrcFrame),
+                                hipHostMallocDefault));
+        c->col_stage_cap = cap;
+    }
+    const unsigned slot = c->col_stage_next++ % vr_ctx::kColStage;
+    VrcFrame* host = c->col_stage + slot * c->col_stage_cap;
+    if (c->col_stage_used[slot]) hip_check(hipEventSynchronize(c->col_stage_ev[slot]));   // the copy that last read the slot
+    std::memcpy(host, m.fcs.data() + b, n * sizeof(VrcFrame));
+    hip_check(hipMemcpyAsync(c->colframes.p, host, n * sizeof(VrcFrame), hipMemcpyHostToDevice, st));
+    hip_check(hipEventRecord(c->col_stage_ev[slot], st));
+    c->col_stage_used[slot] = true;
+    m.up_st = st;
+    m.up_ev = c->col_stage_ev[slot];
+}
+
+// The launches of a call.  Pipelined (vr_options.column_overlap): the first marches kColFirst frames
+// -- nothing hides it, and a short march is a few us less than a long one -- with its frames as kernel
+// arguments, so that it waits for no upload.  The launches after it read their frames from device
+// memory and run beside the expands of the chunk before: a march of n frames takes about 8 + 1.8 n us
+// and the expands of m frames 6.2 m, so each chunk may be kColGrow times the one before and still be
+// marched by the time its expands are due -- 3, 9, 20 for a call of 32 -- up to kColFrames a launch.
+// (kColGrow = 0: kColNext frames each, 0 = all the rest; the sweep's other schedules.)  A launch costs
+// its latency once whatever runs beside it, so few long launches beat many short ones (DESIGN section
+// 5).  Not pipelined: a call of up to kColBatch frames is one launch with kernel arguments, no upload;
+// a longer one marches kColFirst0 frames that way (0: none) and the rest from device memory.
+// Compile-time constants, -D knobs of the experiment builds only (tools/build_ab.sh).
+#ifndef VR_COL_FIRST
+#define VR_COL_FIRST 3
+#endif
+#ifndef VR_COL_GROW
+#define VR_COL_GROW 3
+#endif
+#ifndef VR_COL_NEXT
+#define VR_COL_NEXT 0
+#endif
+#ifndef VR_COL_FIRST0
+#define VR_COL_FIRST0 0
+#endif
+constexpr size_t kColFirst = VR_COL_FIRST, kColGrow = VR_COL_GROW, kColNext = VR_COL_NEXT, kColFirst0 = VR_COL_FIRST0;
+static_assert(kColFirst >= 1 && kColFirst <= (size_t)kColBatch && kColFirst0 <= (size_t)kColBatch &&
+                  kColNext <= (size_t)kColFrames,
+              "the first launch's frames are kernel arguments");
+
+void chunk_columns(ColumnMarches& m, bool overlap) {
+    const size_t n = m.fcs.size(),
+                 first = !overlap && n <= (size_t)kColBatch ? n : std::min(n, overlap ? kColFirst : kColFirst0);
+    const size_t grow = overlap ? kColGrow : 0;
+    size_t next = grow ? first * grow : overlap && kColNext ? kColNext : (size_t)kColFrames;
+    m.chunk.push_back(0);
+    if (first) m.chunk.push_back(first);
+    m.dev_chunk = m.chunk.size() - 1;
+    for (size_t k = first; k < n; next *= std::max<size_t>(1, grow)) {
+        next = std::min<size_t>(next, kColFrames);
+        m.chunk.push_back(k = std::min(n, k + next));
+    }
+}
 
 int vr_render_batch(vr_ctx* c, const vr_params* p, const vr_camera* cams, int32_t n_frames, float* out,
                     int32_t out_flags) {
@@ -2296,18 +2386,22 @@ int vr_render_batch(vr_ctx* c, const vr_params* p, const vr_camera* cams, int32_
         std::vector<ColumnSlice> pre;
         ColumnMarches m;
         plan_columns(c, p, cams, n_frames, rects, m, pre);
-        // vr_options.column_overlap.  0, or one stream: every march first, on the ctx stream, then the
-        // fork.  1: only the first chunk (kColFirst frames) comes before the fork; chunk k + 1's march
-        // is queued when the host reaches chunk k's first frame, ahead of that chunk's expands, on the
-        // in-flight stream (k + 1) mod ns -- that stream's frames of chunk k wait behind it while the
-        // other streams expand.  Chunk k's expands wait for col_ev[k & 1], recorded behind its march
-        // (and recorded again, for chunk k + 2, only after those waits are queued); on the stream that
-        // marched the chunk, stream order does.  No stream but the in-flight ones, which the call joins.
+        // vr_options.column_overlap.  0, or one stream: the upload and every march first, on the ctx
+        // stream, then the fork.  1: only the first chunk (kColFirst frames) comes before the fork; chunk
+        // k + 1's march is queued when the host reaches chunk k's first frame, ahead of that chunk's
+        // expands, on the in-flight stream (k + 1) mod ns -- that stream's frames of chunk k wait behind
+        // it while the other streams expand -- and the upload directly ahead of chunk 1's march there.
+        // Chunk k's expands wait for col_ev[k & 1], recorded behind its march (and recorded again, for
+        // chunk k + 2, only after those waits are queued); on the stream that marched the chunk, stream
+        // order does.  No stream but the in-flight ones, which the call joins.
         const int ns = in_flight_streams(c, n_frames);
         const bool overlap = ns > 1 && !m.fcs.empty() && c->opt.column_overlap != 0;
-        for (size_t k = 0; k < m.fcs.size(); k += (overlap && k == 0) ? kColFirst : (size_t)kColBatch) m.chunk.push_back(k);
-        m.chunk.push_back(m.fcs.size());
-        const size_t nchunk = m.chunk.size() - 1;
+        size_t nchunk = 0;
+        if (!m.fcs.empty()) {
+            chunk_columns(m, overlap);
+            nchunk = m.chunk.size() - 1;
+            if (!overlap && m.dev_chunk < nchunk) upload_columns(c, m, c->stream);
+        }
         for (size_t k = 0; k < (overlap ? std::min<size_t>(1, nchunk) : nchunk); ++k) march_columns(c, m, k, c->stream);
         std::vector<int> chunk_of((size_t)n_frames, -1);   // frame -> the chunk it opens
         if (overlap && nchunk > 1) {
@@ -2320,6 +2414,7 @@ int vr_render_batch(vr_ctx* c, const vr_params* p, const vr_camera* cams, int32_
             if (chunk_of[(size_t)f] >= 0) {
                 const size_t k = (size_t)chunk_of[(size_t)f];
                 if (k + 1 < nchunk) {
+                    if (k + 1 == m.dev_chunk) upload_columns(c, m, in_flight(k + 1));
                     march_columns(c, m, k + 1, in_flight(k + 1));
                     hip_check(hipEventRecord(c->col_ev[(k + 1) & 1], in_flight(k + 1)));
                 }

@@ -120,6 +120,9 @@ struct ColBatch {
     VrcFrame f[kColBatch];
 };
 static_assert(sizeof(ColBatch) + 256 <= 4096, "ColBatch must fit the kernel argument segment");
+// The frames of one launch when the march reads them from an array in device memory (vrc_march_kernel,
+// DEVF): nothing but the grid's y extent bounds it; a call beyond it takes one more launch
+constexpr int kColFrames = 32;
 
 // Per-frame constants of the TEST march (kernel.cu:72-187).
 struct TestFrame {

@@ -459,14 +459,19 @@ __device__ __forceinline__ void axis1_table(const VrcFrame& f, int ma, bool cell
 }
 
 // The frame argument of vrc_march_kernel: the frame, or for the column march (COLS) the frames of a
-// batch (vr_device.h ColBatch), of which workgroup row blockIdx.y marches one
-template <bool COLS> struct FrameArg { using type = VrcFrame; };
-template <> struct FrameArg<true> { using type = ColBatch; };
+// launch, of which workgroup row blockIdx.y marches one -- by value (vr_device.h ColBatch), or (DEVF) an
+// array in device memory.  The __restrict__ of that kernel parameter is what lets the compiler read
+// the frame's fields with scalar loads, like kernel arguments (without it each is a vector load per
+// lane); the frame is only ever used through the reference, never copied to a local
+template <bool COLS, bool DEVF = false> struct FrameArg { using type = VrcFrame; };
+template <> struct FrameArg<true, false> { using type = ColBatch; };
+template <> struct FrameArg<true, true> { using type = const VrcFrame* __restrict__; };
 __device__ __forceinline__ const VrcFrame& frame_arg(const VrcFrame& fa) { return fa; }
 __device__ __forceinline__ const VrcFrame& frame_arg(const ColBatch& fa) { return fa.f[blockIdx.y]; }
+__device__ __forceinline__ const VrcFrame& frame_arg(const VrcFrame* __restrict__ fa) { return fa[blockIdx.y]; }
 
-template <bool F2B, bool ESS, bool IDX64, int GEOM, int K, bool SHADE, int STATS = 0, bool COLS = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves<GEOM, ESS, K, SHADE>()))) void vrc_march_kernel(typename FrameArg<COLS>::type fa, const WorkTile* __restrict__ work,
+template <bool F2B, bool ESS, bool IDX64, int GEOM, int K, bool SHADE, int STATS = 0, bool COLS = false, bool DEVF = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves<GEOM, ESS, K, SHADE>()))) void vrc_march_kernel(typename FrameArg<COLS, DEVF>::type fa, const WorkTile* __restrict__ work,
                                                         const int32_t* __restrict__ order,
                                                         const uint8_t* __restrict__ cls,
                                                         const int32_t* __restrict__ gmaps,
@@ -485,7 +490,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
     // COLS: the column marches of up to kColBatch frames in one launch (vr_render_batch), grid y =
     // frame: every frame's constants are kernel arguments (fa.f[blockIdx.y]: scalar loads at a
     // wave-uniform offset of the kernarg segment, like the single frame's), its columns stored
-    // f.col_ofs float4s into the call's column buffer
+    // f.col_ofs float4s into the call's column buffer.  DEVF: up to kColFrames frames, fa[blockIdx.y]
+    // in device memory (scalar loads all the same: see FrameArg)
     const VrcFrame& f = frame_arg(fa);
     if constexpr (COLS) out += f.col_ofs;
     constexpr bool AXIS1 = GEOM == kGeomAxis1 || GEOM == kGeomAxis1Run || GEOM == kGeomAxis1Z;
@@ -1569,7 +1575,7 @@ size_t vrc_axis1_table_bytes(const VrcFrame& f, int batch) {
     return (n_tab * (f.tsplit ? 8 : 4) + (size_t)f.ncell * 4 + n_tab + 3) & ~(size_t)3;
 }
 
-template <int STATS, int K, bool COLS = false>
+template <int STATS, int K, bool COLS = false, bool DEVF = false>
 static void launch_vrc_variant(const VrcFrame& f, const WorkTile* work, const int32_t* order, int n_blocks_in,
                                const uint8_t* cls, const int32_t* maps, const int64_t* mapx64, const uint32_t* occ,
                                const float4* tf, int n_tf, float4* out, unsigned long long* stats, hipStream_t st,
@@ -1583,16 +1589,19 @@ static void launch_vrc_variant(const VrcFrame& f, const WorkTile* work, const in
     // f.persist_wgs > 0: persistent grid of 256 CUs x persist_wgs workgroups (multiple of 8)
     int n_blocks = n_blocks_in;
     if (f.persist_wgs > 0) n_blocks = std::min(n_blocks_in, 256 * f.persist_wgs);
-    // the kernel's frame argument: f, or (COLS) the n_frames <= kColBatch frames of the launch, f first
-    typename FrameArg<COLS>::type fa;
-    if constexpr (COLS) {
+    // the kernel's frame argument: f, or (COLS) the n_frames <= kColBatch frames of the launch, f first,
+    // or (DEVF) colframes = their copies in device memory (f: the host's copy of the first)
+    typename FrameArg<COLS, DEVF>::type fa;
+    if constexpr (DEVF) {
+        fa = colframes;
+    } else if constexpr (COLS) {
         std::memset(&fa, 0, sizeof fa);
         for (int i = 0; i < n_frames; ++i) fa.f[i] = colframes[i];
     } else {
         fa = f;
     }
 #define VR_L(F2B_, ESS_, I64_, AX_, SH_)                                                                    \
-    hipLaunchKernelGGL((vrc_march_kernel<F2B_, ESS_, I64_, AX_, K, SH_, STATS, COLS>), dim3(n_blocks, n_frames), dim3(kWgThreads), \
+    hipLaunchKernelGGL((vrc_march_kernel<F2B_, ESS_, I64_, AX_, K, SH_, STATS, COLS, DEVF>), dim3(n_blocks, n_frames), dim3(kWgThreads), \
                        lds, st, fa, work, order, cls, maps, mapx64, occ, tf, n_tf, out, stats, vol, rawmaps, occcol, cdist, gtab, gtab_out)
 #define VR_L2(I64_, AX_, SH_)                                                                            \
     if (f2b) { if (ess) VR_L(true, true, I64_, AX_, SH_); else VR_L(true, false, I64_, AX_, SH_); } \
@@ -2087,12 +2096,26 @@ hipError_t launch_axis_expand(const VrcFrame& f, const WorkTile* work, int n_blo
 // 16 x 16 tiles) into colbuf[col_ofs + (i0 - col_i0) * col_n1 + (i1 - col_i1)]: the marches of the
 // n_frames <= kColBatch frames fs[] in one launch (grid y).  All take the first one's kernel variant
 // and LDS size (host: same params, view axis, table form), and n_blocks = their common n_slots covers
-// the largest rectangle.
+// the largest rectangle.  dev_frames: null, or the copies of fs[0 .. n_frames), n_frames <= kColFrames,
+// in device memory (complete in stream order ahead of this launch), which the kernel then reads
+// in place of kernel arguments.
 hipError_t launch_vrc_columns(const VrcFrame* fs, int n_frames, int n_blocks, const uint8_t* cls, const int32_t* maps,
                               const float4* tf, int n_tf, float4* colbuf, hipStream_t st, int batch,
-                              const unsigned long long* occcol, const int32_t* gtab, int32_t* gtab_out) {
-    if (n_frames < 1 || n_frames > kColBatch) return hipErrorInvalidValue;
+                              const unsigned long long* occcol, const int32_t* gtab, int32_t* gtab_out,
+                              const VrcFrame* dev_frames) {
+    if (n_frames < 1 || n_frames > (dev_frames ? kColFrames : kColBatch)) return hipErrorInvalidValue;
     const VrcFrame& f = fs[0];
+    if (dev_frames) {
+        if (vrc_batch(f, batch) == 16)
+            launch_vrc_variant<0, 16, true, true>(f, nullptr, nullptr, n_blocks, cls, maps, nullptr, nullptr, tf, n_tf,
+                                                  colbuf, nullptr, st, nullptr, nullptr, occcol, nullptr, gtab,
+                                                  gtab_out, dev_frames, n_frames);
+        else
+            launch_vrc_variant<0, 8, true, true>(f, nullptr, nullptr, n_blocks, cls, maps, nullptr, nullptr, tf, n_tf,
+                                                 colbuf, nullptr, st, nullptr, nullptr, occcol, nullptr, gtab,
+                                                 gtab_out, dev_frames, n_frames);
+        return hipGetLastError();
+    }
     const VrcFrame* colframes = fs;
     if (vrc_batch(f, batch) == 16)
         launch_vrc_variant<0, 16, true>(f, nullptr, nullptr, n_blocks, cls, maps, nullptr, nullptr, tf, n_tf, colbuf,
