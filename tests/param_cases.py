@@ -8,7 +8,7 @@ built on first use (gpu_camera, gpu_params).
 
 References: VRC is the oracle's octree march (OracleOctree.render_vrc; render_vrc_shaded for a case
 with shading coefficients), TEST oracle.render_test, DVR
-tests/dvr_ref.py.  A volume with non-finite voxels takes the closed-form octree (implicit=True): the
+tests/dvr_ref.py, MIP tests/mip_ref.py.  A volume with non-finite voxels takes the closed-form octree (implicit=True): the
 literal tree's search recurses past its leaves when max == min is false (NaN), the closed form
 returns x > 0 ? x : 0 -- what the library's classify kernel states -- and equals the literal tree bit
 for bit on finite volumes (tests/test_param_cases.py, tests/test_oracle_pin.py).
@@ -16,12 +16,13 @@ for bit on finite volumes (tests/test_param_cases.py, tests/test_oracle_pin.py).
 import numpy as np
 
 import dvr_ref
+import mip_ref
 import oracle
 
 F = np.float32
-VRC, TEST, DVR = 1, 5, 6          # vr_api.h VR_MODE_*
+VRC, TEST, DVR, MIP = 1, 5, 6, 7  # vr_api.h VR_MODE_*
 SHADE, CONIC = 8, 16              # vr_api.h VR_FLAG_SHADE, VR_FLAG_CONIC
-MODES = {"vrc": VRC, "test": TEST, "dvr": DVR}
+MODES = {"vrc": VRC, "test": TEST, "dvr": DVR, "mip": MIP}
 
 W, H, S = 48, 36, 64              # the frame of every case but the tiny shapes
 RSW = 2.0
@@ -112,6 +113,19 @@ def blob_special():
     return vol
 
 
+SUBNORMAL_SCALE = 2.0 ** -140
+SUBNORMAL_CAL = 255.0 * 2.0 ** -140   # (a double: the value is below float32's normal range)
+
+
+def blob_subnormal():
+    """blob() * 2^-140: every voxel an exact subnormal float32 (k * 2^-140, k = 0..255), so a march that
+    flushes subnormals -- on a load, in a lerp or in a compare -- renders the all-zero volume instead.
+    With cal_max = SUBNORMAL_CAL the normalised values are blob()'s k / 255."""
+    vol = blob() * F(SUBNORMAL_SCALE)
+    assert vol.dtype == F
+    return vol
+
+
 def cube():
     """(32, 17, 32): integers 0..255, those below 120 zeroed.  x and z fill the octree cube and no face
     is empty, so the one-sided differences of the shading stage at the six faces are visible."""
@@ -134,6 +148,16 @@ def deep_cases(view, **kw):
     narrow = Case(view, VRC, rsw=0.02, sd=0.002, fc=centre - 0.048, frame=(TW, TH, TS), **kw)
     wide = Case(view, VRC, rsw=1.2, frame=(TW, TH, TS), **kw)
     return [narrow] if view == "obl" else [wide, narrow]
+
+
+def deep_volume_cases(mode):
+    """The frames of a deep shape in DVR and MIP (no sample distance or front clip there: the ray is the
+    viewplane distance long).  The 1.2 screen sees the needle along z, x and y_back and steps over it
+    along obl -- a frame of background through the whole march, kept as a case -- and the 0.02 screen
+    draws along obl (tests/test_param_cases.py)."""
+    frame = (TW, TH, TS)
+    return [Case(view, mode, rsw=1.2, frame=frame) for view in ("z", "x", "y_back", "obl")] + \
+        [Case("obl", mode, rsw=0.02, frame=frame)]
 
 
 def default_tf():
@@ -234,6 +258,7 @@ class Reference:
             raise ValueError("the literal octree's search does not terminate on non-finite voxels")
         self._octree = None
         self._frames = {}
+        self._mips = {}
 
     @property
     def octree(self):
@@ -251,11 +276,23 @@ class Reference:
                 f = self.octree.render_vrc(self.cal, self.otf, p, cam)
             elif case.mode == TEST:
                 f = oracle.render_test(self.vol, self.cal, self.otf, p, cam)
+            elif case.mode == MIP:
+                f = self.mip(case)[0]
             else:
                 f = dvr_ref.render(self.vol, self.cal, self.tf, p, cam)
             f.setflags(write=False)
             self._frames[k] = f
         return self._frames[k]
+
+    def mip(self, case):
+        """mip_ref.render's (frame, m, hit) of a MIP case: the running maximum and the in-volume mask too."""
+        k = case.key()
+        if k not in self._mips:
+            out = mip_ref.render(self.vol, self.cal, case.oracle_params(), case.oracle_camera())
+            for a in out:
+                a.setflags(write=False)
+            self._mips[k] = out
+        return self._mips[k]
 
     def count_in_samples(self, case):
         return self.octree.count_in_samples(case.oracle_params(), case.oracle_camera())
@@ -267,7 +304,7 @@ _SHARED = {}
 def shared_reference(name):
     """The Reference of a named volume, one per process: "blob", "avg152", "special" / "special200"
     (blob_special at cal_max 255 / 200.7, closed-form octree), "special_tf0" (blob_special under
-    tf_zero_visible), "cube", "deep_x" / "deep_z" (closed-form octree)."""
+    tf_zero_visible), "cube", "subnormal" (blob_subnormal at SUBNORMAL_CAL; DVR and MIP only), "deep_x" / "deep_z" (closed-form octree)."""
     if name not in _SHARED:
         if name == "blob":
             _SHARED[name] = Reference(blob(), 255.0)
@@ -279,6 +316,8 @@ def shared_reference(name):
             _SHARED[name] = Reference(blob_special(), 255.0, tf=tf_zero_visible(), literal=False)
         elif name == "cube":
             _SHARED[name] = Reference(cube(), 255.0)
+        elif name == "subnormal":
+            _SHARED[name] = Reference(blob_subnormal(), SUBNORMAL_CAL, literal=False)
         elif name in DEEP:   # (a literal octree of depth 11 is out of reach: closed form)
             _SHARED[name] = Reference(tiny_volume(DEEP[name]), 255.0, literal=False)
         elif name == "avg152":

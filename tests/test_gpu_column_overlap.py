@@ -72,6 +72,9 @@ def _call(a, cams, fill=0.0, asynchronous=False):
     for cam in cams:
         assert a.axis_columns_plan(_p(), cam)["columns"]
     out = torch.full((len(cams), W, H, 4), fill, dtype=torch.float32, device="cuda:0")
+    # the fill runs on torch's stream, the call on the context's own non-blocking one: wait for the fill
+    # alone -- torch's stream, not the device, so the context's queued calls stay in flight
+    torch.cuda.current_stream().synchronize()
     a.render_batch_device(_p(), cams, out.data_ptr(), asynchronous=asynchronous)
     return out
 

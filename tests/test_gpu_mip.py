@@ -105,6 +105,24 @@ def test_edge_clamp_cube_filling_volume(oracle_mod):
                 check_all_flags(r, ref, W, H, S, cam, name)
 
 
+@pytest.mark.parametrize("S", [4088, 4089, 9000])
+def test_long_rays(avg152, oracle_mod, S):
+    """The per-frame B table in LDS is kept while S + 8 <= kMaxTestTab = 4096: S = 4088 is the last frame
+    with it, 4089 the first whose positions are all computed per sample (the same expressions), 9000
+    TEST's long-ray size.  Adjacent samples are 0.02 voxel apart here, so a cell jump covers hundreds of
+    them.  Bitwise in all four flag combinations, from the byte copy and from the float volume."""
+    vol, cal = avg152
+    W, H = 20, 14
+    with vr.VolumeRenderer(vol, cal, device=0) as a, \
+            vr.VolumeRenderer(vol, cal, device=0, options=vr.default_options(dvr_volume=1)) as b:
+        for name in ("reset", "default"):
+            cam, _ = camera_pair(oracle_mod, name, W, H)
+            ref, m, hit = reference(oracle_mod, "avg", vol, cal, W, H, S, name)
+            assert hit.sum() >= 80 and len(np.unique(m[hit])) > 50, name   # (135 / 87 and 90 / 64)
+            check_all_flags(a, ref, W, H, S, cam, ("byte", S, name))
+            check_all_flags(b, ref, W, H, S, cam, ("float", S, name))
+
+
 @pytest.mark.parametrize("kind", ["negative", "nonfinite"])
 def test_negative_and_non_finite_voxels(oracle_mod, kind):
     rng = np.random.default_rng(9)

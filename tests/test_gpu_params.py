@@ -1,10 +1,11 @@
 """Non-default render parameters on the GPU: sample distance and front clip (VRC), viewplane distance
-(TEST, DVR), anamorphic and far screens, backgrounds, ERT epsilons and a fractional cal_max, on every
-specialised march, against the references of tests/param_cases.py (which tests/test_param_cases.py
-keeps from being vacuous).
+(TEST, DVR, MIP), anamorphic and far screens, backgrounds, ERT epsilons and a fractional cal_max, on
+every specialised march, against the references of tests/param_cases.py (which
+tests/test_param_cases.py keeps from being vacuous).
 
 The project's rules: exact frames (flags 0) are the reference's values bit for bit, ESS alone equals
 the exact frame, ERT and ESS | ERT at the default epsilon, background and TF are within TOL = 1e-4.
+VR_MODE_MIP has no tolerance: all four flag combinations give the exact frame (check_flags_mip).
 Values are compared with np.array_equal, not bit patterns: a background of -0.0 legitimately comes
 back as +0.0 from a marched pixel.
 """
@@ -13,7 +14,7 @@ import pytest
 
 import param_cases as pc
 import volumerenderingproject_amd as vr
-from param_cases import DVR, TEST, VRC, Case
+from param_cases import DVR, MIP, TEST, VRC, Case
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +43,25 @@ def check_flags(r, ref, case, what):
         assert err <= TOL, (what, "flags", fl, err)
         assert np.all(fast[..., 3] == 1.0), (what, fl)
     return exact
+
+
+def check_flags_mip(r, ref, case, what):
+    """VR_MODE_MIP: flags 0 == ref, and ESS, ERT and ESS | ERT == the flags-0 frame -- a skipped sample
+    is one that could not have replaced the maximum, so there is no tolerance -- alpha 1.  Returns the
+    exact frame."""
+    assert case.mode == MIP
+    cam = case.gpu_camera()
+    exact = r.render(case.gpu_params(0), cam)
+    assert_same(exact, ref, (what, "exact"))
+    assert np.all(exact[..., 3] == 1.0), what
+    for fl in (E, T, E | T):
+        assert_same(r.render(case.gpu_params(fl), cam), exact, (what, "flags", fl))
+    return exact
+
+
+def check_mode(r, ref, case, what):
+    """check_flags_mip for a MIP case, check_flags for every other mode."""
+    return (check_flags_mip if case.mode == MIP else check_flags)(r, ref, case, what)
 
 
 def ert_bound(tf, bg, eps, S):
@@ -128,6 +148,8 @@ TEST_DVR_CONTEXTS = {
     "test_corners3": (TEST, {"test_corners": 3}),
     "dvr_auto": (DVR, {"dvr_volume": 0}),
     "dvr_float": (DVR, {"dvr_volume": 1}),
+    "mip_auto": (MIP, {"dvr_volume": 0}),
+    "mip_float": (MIP, {"dvr_volume": 1}),
     "vrc_screens": (VRC, {}),
 }
 
@@ -141,11 +163,11 @@ def test_test_and_dvr_viewplane_and_screen(ctx):
             for vpd, scale in pc.VPD:
                 for view in pc.VIEWS:
                     case = Case(view, mode, vpd=vpd, scale=scale)
-                    check_flags(r, ref.frame(case), case, (ctx, "vpd", vpd, scale, view))
+                    check_mode(r, ref.frame(case), case, (ctx, "vpd", vpd, scale, view))
         for rsw, rsh in pc.SCREENS:
             for view in pc.VIEWS:
                 case = Case(view, mode, rsw=rsw, rsh=rsh)
-                check_flags(r, ref.frame(case), case, (ctx, "screen", rsw, rsh, view))
+                check_mode(r, ref.frame(case), case, (ctx, "screen", rsw, rsh, view))
 
 
 BACKGROUNDS = [(0.7, -0.25, 1.5, 0.3), (0.0, 0.0, 0.0, 0.0), (1e6, 1e-30, 0.5, 9.0)]
@@ -162,13 +184,16 @@ def test_background_is_honoured(bg):
     rs = {cull: vr.VolumeRenderer(ref.vol, ref.cal, device=0, options=vr.default_options(cull=cull))
           for cull in (0, 1, 2)}
     try:
-        for mode in (VRC, TEST, DVR):
+        for mode in (VRC, TEST, DVR, MIP):
             for view in ("z", "obl"):
                 case = Case(view, mode, bg=bg)
                 want = ref.frame(case)
                 assert np.all(want[..., 3] == 1.0)
                 cam = case.gpu_camera()
                 for cull, r in rs.items():
+                    if mode == MIP:   # every flag combination bitwise: the background is a pixel's whole value or no part of it
+                        check_flags_mip(r, want, case, (mode, view, "cull", cull))
+                        continue
                     exact = r.render(case.gpu_params(0), cam)
                     assert_same(exact, want, (mode, view, "cull", cull))
                     assert_same(r.render(case.gpu_params(E), cam), exact, (mode, view, "cull", cull, "ess"))
@@ -185,6 +210,7 @@ def test_background_is_honoured(bg):
                 for ids in (np.arange(nt, dtype=np.int32), r.visible_tiles(p, cam, tw, th)):
                     tiles = torch.zeros((max(1, len(ids)), tw * th, 3), dtype=torch.float32, device="cuda:0")
                     frame = torch.full((pc.W, pc.H, 4), -7.0, dtype=torch.float32, device="cuda:0")
+                    torch.cuda.current_stream().synchronize()   # (the fills run on torch's stream, the context's is non-blocking)
                     if len(ids) == nt:
                         assert r.render_tiles(p, cam, tw, th, 0, 1, tiles.data_ptr(), rgb=True) == nt
                     else:
@@ -236,7 +262,9 @@ def test_ert_epsilon(mode):
 
 @pytest.mark.parametrize("cal", [200.7, 1000.25])
 def test_cal_max_not_an_integer(cal):
-    """VRC divides by (float)(int)cal_max, TEST and DVR by the double."""
+    """VRC divides by (float)(int)cal_max, TEST, DVR and MIP by the double.  MIP at 200.7: the clamp
+    min(max(m / cal_max, 0), 1) is hit from above on some in-volume pixels and not on others (the
+    blob's voxels reach 255)."""
     ref = pc.Reference(pc.blob(), cal)
     with vr.VolumeRenderer(ref.vol, cal, device=0) as r:
         for mode in (VRC, TEST, DVR):
@@ -245,6 +273,15 @@ def test_cal_max_not_an_integer(cal):
                 got = r.render(case.gpu_params(0), case.gpu_camera())
                 assert_same(got, ref.frame(case), (cal, mode, view))
                 assert pc.non_background(got) >= 40
+        for view in ("z", "obl"):
+            case = Case(view, MIP)
+            got = check_flags_mip(r, ref.frame(case), case, (cal, "mip", view))
+            g = got[..., 0][ref.mip(case)[2]]   # the in-volume pixels
+            assert g.size >= 140
+            if cal == 200.7:
+                assert int((g == 1.0).sum()) >= 90 and int(((g > 0.0) & (g < 1.0)).sum()) >= 140, (view, g.size)
+            else:
+                assert np.all(g < 1.0), view
     # and the two divisors differ: at 200.7 some voxel changes class between them
     if cal == 200.7:
         v = np.arange(256, dtype=F)

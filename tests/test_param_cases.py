@@ -1,16 +1,19 @@
 """The off-default cases of tests/param_cases.py on the CPU (oracle and dvr_ref only, no GPU): every
 case draws something and leaves background, the tiny shapes are visible, the special voxels change
-the frame, the closed-form octree equals the literal one where both exist, and the DVR restatement
-stays pinned to the oracle off the default viewplane distance."""
+the frame, the closed-form octree equals the literal one where both exist, the DVR restatement
+stays pinned to the oracle off the default viewplane distance, and the same cases draw in VR_MODE_MIP
+(mip_ref): enough in-volume pixels and different maxima, clamped and unclamped pixels at a fractional
+cal_max, the deep shapes, and a volume of subnormals that is not the zero volume."""
 import numpy as np
 import pytest
 
 import dvr_ref
 import oracle
 import param_cases as pc
-from param_cases import DVR, TEST, VRC, Case
+from param_cases import DVR, MIP, TEST, VRC, Case
 
 MIN_PIXELS = 40
+F32 = np.float32
 
 
 def check_content(frame, what):
@@ -100,6 +103,110 @@ def test_zero_visible_tf_tells_nan_from_zero():
             assert np.all(np.isfinite(fa))
             n = int(np.any(fa != fb, axis=-1).sum())
             assert (n >= 5) if differ else (n == 0), (differ, view, n)   # (50 NaN voxels; a few pixels suffice)
+
+
+# ---- VR_MODE_MIP and the DVR / MIP volumes: the cases of tests/test_gpu_params.py and
+# tests/test_gpu_volumes.py are not vacuous.  The floors are round numbers under what mip_ref /
+# dvr_ref give (>= 1 where that is 1).
+
+def check_mip_content(ref, case, what):
+    """At least 140 in-volume pixels with at least 90 different maxima among them."""
+    f, m, hit = ref.mip(case)
+    assert f is ref.frame(case) and np.all(np.isfinite(f)) and np.all(f[..., 3] == 1.0), what
+    assert int(hit.sum()) >= 140, (what, int(hit.sum()))
+    assert len(np.unique(m[hit])) >= 90, (what, len(np.unique(m[hit])))
+    return f, m, hit
+
+
+@pytest.mark.parametrize("vpd,scale", pc.VPD)
+def test_mip_vpd_cases_draw(vpd, scale):
+    ref = pc.shared_reference("blob")
+    for view in pc.VIEWS:
+        check_mip_content(ref, Case(view, MIP, vpd=vpd, scale=scale), (vpd, scale, view))
+
+
+@pytest.mark.parametrize("rsw,rsh", pc.SCREENS)
+def test_mip_screen_cases_draw(rsw, rsh):
+    ref = pc.shared_reference("blob")
+    for view in pc.VIEWS:
+        check_mip_content(ref, Case(view, MIP, rsw=rsw, rsh=rsh), (rsw, rsh, view))
+
+
+def test_mip_fractional_cal_max_clamps_some_pixels_only():
+    """cal_max = 200.7: min(max(m / cal_max, 0), 1) is hit from above on some in-volume pixels and
+    not on others (z: 149 inside (0, 1) and 91 at 1; obl: 298 and 93)."""
+    ref = pc.Reference(pc.blob(), 200.7)
+    for view, inner, clamped in (("z", 140, 90), ("obl", 290, 90)):
+        f, m, hit = ref.mip(Case(view, MIP))
+        g = f[..., 0][hit]
+        assert int(((g > 0) & (g < 1)).sum()) >= inner, (view, int(((g > 0) & (g < 1)).sum()))
+        assert int((g == 1).sum()) >= clamped, (view, int((g == 1).sum()))
+        assert np.all(m[hit][g == 1] >= F32(200.7))
+
+
+@pytest.mark.parametrize("shape", list(pc.TINY))
+def test_tiny_shapes_are_visible_in_mip(shape):
+    """(the minimum is one pixel, (65, 3, 2) along x)"""
+    ref = pc.Reference(pc.tiny_volume(shape), 255.0)
+    for view in ("z", "x", "y_back", "obl"):
+        f, m, hit = ref.mip(Case(view, MIP, rsw=pc.TINY[shape], frame=(pc.TW, pc.TH, pc.TS)))
+        assert np.all(np.isfinite(f))
+        assert int(hit.sum()) >= 1, (shape, view)
+
+
+@pytest.mark.parametrize("name", ["special", "special200"])
+def test_special_voxels_reach_mip(name):
+    ref = pc.shared_reference(name)
+    for view in pc.VIEWS:
+        f, m, hit = ref.mip(Case(view, MIP))
+        assert np.all(np.isfinite(f)), (name, view)
+        assert len(np.unique(m[hit])) >= 180, (name, view, len(np.unique(m[hit])))
+        assert int((f[..., 0][hit] == 1).sum()) >= 90, (name, view)   # (1e30, 3.4e38, 255.5, 256: clamped)
+
+
+@pytest.mark.parametrize("name", list(pc.DEEP))
+def test_deep_shapes_in_dvr_and_mip(name):
+    """The 1.2 screen draws along z, x and y_back in both modes (MIP: 1 to 33 pixels) and nothing along
+    obl; the 0.02 screen draws along obl (MIP: 12 pixels on deep_x, 17 on deep_z; DVR: 7 and 9)."""
+    ref = pc.shared_reference(name)
+    for mode in (DVR, MIP):
+        for case in pc.deep_volume_cases(mode):
+            f = ref.frame(case)
+            assert np.all(np.isfinite(f))
+            n = int(ref.mip(case)[2].sum()) if mode == MIP else pc.non_background(f)
+            if case.view == "obl" and case.rsw == 1.2:
+                assert n == 0, (name, mode, n)
+            elif case.view == "obl":
+                assert n >= (10 if mode == MIP else 5), (name, mode, n)
+            else:
+                assert n >= 1, (name, mode, case.view, n)
+
+
+def test_subnormal_volume_is_not_the_zero_volume():
+    """blob_subnormal(): every voxel k * 2^-140, an exact subnormal.  Its DVR and MIP frames draw, and
+    they are not the frames of the all-zero volume -- what a march that flushes subnormals to zero
+    renders.  The byte copy is not taken (no voxel but 0 is an integer), so the float gathers are the
+    path under test."""
+    ref = pc.shared_reference("subnormal")
+    v = ref.vol
+    nz = v[v != 0]
+    assert nz.size >= 10000 and np.all(nz > 0) and np.all(nz < F32(2.0 ** -126))
+    assert np.array_equal(v.astype(np.float64) * 2.0 ** 140, pc.blob().astype(np.float64))   # exact multiples
+    # the gate of dvr_bytes_kernel: every voxel an integer in 0..255
+    with np.errstate(invalid="ignore"):
+        lossless = (v >= 0) & (v <= 255) & (v.astype(np.int32).astype(F32) == v)
+    assert not np.all(lossless)
+    zero = pc.Reference(np.zeros_like(v), pc.SUBNORMAL_CAL, literal=False)
+    for view in ("z", "x", "obl"):
+        for mode in (DVR, MIP):
+            case = Case(view, mode)
+            f = ref.frame(case)
+            assert np.all(np.isfinite(f)), (view, mode)
+            assert pc.non_background(f) >= MIN_PIXELS, (view, mode, pc.non_background(f))
+            changed = int(np.any(f != zero.frame(case), axis=-1).sum())
+            assert changed >= MIN_PIXELS, (view, mode, changed)
+        f, m, hit = ref.mip(Case(view, MIP))
+        assert len(np.unique(m[hit])) >= 90 and np.all(m[hit] < F32(2.0 ** -126)), view
 
 
 # ---- the shading stage (VR_FLAG_SHADE): the cases of tests/test_gpu_shade.py are not vacuous ----
