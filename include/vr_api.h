@@ -76,6 +76,47 @@ extern "C" {
                               cal_max must be finite and > 0 (VR_EINVAL at render); the size limit is
                               VR_MODE_DVR's (VR_ERANGE).  vr_count_samples / vr_count_marched /
                               vr_count_work: VR_EINVAL; vr_axis_columns_plan reports no column path      */
+#define VR_MODE_ISO 8      /* shaded first-hit isosurface of the same trilinear field at the context's isovalue
+                              (vr_set_isosurface; no reference mode).  All arithmetic is float32, every
+                              operation rounded on its own (no contraction, IEEE division and square root).
+                              1. Samples: VR_MODE_DVR's positions p(x, y, s), in-volume test 0 <= p_a < d_a
+                              and value v, operation for operation (corners (int)p and min((int)p + 1,
+                              d - 1), weights p - (int)p, a non-finite voxel reads as 0, the lerp
+                              a*(1 - w) + b*w in y, then x, then z).  The position chain is evaluated at a
+                              float sample coordinate fs: the march uses fs = (float)s, the refinement
+                              fractional fs.
+                              2. Hit: s_h = the smallest s in [0, S) whose sample is in the volume with
+                              v >= iso (a NaN never hits).  Without a hit the pixel is the background's
+                              r, g, b with alpha 1.
+                              3. Refinement, only when s_h > 0 and sample s_h - 1 is in the volume (else
+                              hi = (float)s_h): lo = (float)(s_h - 1), hi = (float)s_h, then VR_ISO_REFINE
+                              rounds of mid = (lo + hi) * 0.5f (exact); the value at p(x, y, mid): in the
+                              volume and >= iso sets hi = mid, otherwise lo = mid.  The surface point is
+                              p* = p(x, y, hi).
+                              4. Gradient, per axis a: q+ = min(p*_a + 1.0f, (float)(d_a - 1)),
+                              q- = max(p*_a - 1.0f, 0.0f), v+ / v- the value at p* with coordinate a
+                              replaced by q+ / q-, span = q+ - q-, g_a = span > 0 ? (v+ - v-) / span : 0;
+                              len2 = (gx*gx + gy*gy) + gz*gz; if len2 > 0: inv = 1.0f / sqrtf(len2) and
+                              N = (-gx*inv, -gy*inv, -gz*inv), otherwise there is no normal.
+                              5. Light, a headlight along the ray in voxel space:
+                              e = p(x, y, S > 1 ? S - 1 : 0) - p(x, y, 0), n2 = (ex*ex + ey*ey) + ez*ez; if
+                              n2 > 0: L = -e * (1.0f / sqrtf(n2)), otherwise there is no light direction.
+                              6. Colour, VR_FLAG_SHADE's law with ka, kd, ks, shininess = vr_params.shade_*:
+                              with a normal and a light ndl = (Nx*Lx + Ny*Ly) + Nz*Lz, d = max(ndl, 0),
+                              spec = d > 0 ? ks * d^shininess : (shininess == 0 ? ks : 0), d^shininess as
+                              exp2(shininess * log2 d) on the hardware transcendentals; without either
+                              d = 1, spec = 0.  Each channel is rgb_c * (ka + kd*d) + spec, unclamped
+                              (egress clamps); alpha is 1.
+                              7. Flags: VR_FLAG_ESS (a ray skips the cells whose upper bound is < iso) and
+                              VR_FLAG_ERT (the march always stops at the hit) are accepted and change no
+                              value: the four combinations give the same frame bit for bit.
+                              VR_FLAG_SHADE / VR_FLAG_CONIC are VR_EINVAL (the mode always shades).
+                              8. cal_max must be finite and > 0 (VR_EINVAL at render); the size limit is
+                              VR_MODE_DVR's (VR_ERANGE).  vr_count_samples / vr_count_marched /
+                              vr_count_work: VR_EINVAL; vr_axis_columns_plan reports no column path; culling
+                              and vr_visible_tiles as for VR_MODE_MIP.  The transfer function plays no
+                              part.                                                                     */
+#define VR_ISO_REFINE 6    /* VR_MODE_ISO: bisection rounds between samples s_h - 1 and s_h             */
 
 /* ---- render flags -------------------------------------------------------------------------- */
 #define VR_FLAG_ESS 1      /* empty-space skipping (bitwise exact: skips only alpha-0 samples)  */
@@ -112,7 +153,7 @@ typedef struct {
 
 /* AppData render fields (utils.h:36-74) made runtime.  vr_params_default fills the reference's
  * values for a given W, H, S.  Every finite value is defined: a zero or negative sample_distance
- * (VRC: S copies of one point / the march runs backwards) and viewplane_distance (TEST, DVR, MIP) render
+ * (VRC: S copies of one point / the march runs backwards) and viewplane_distance (TEST, DVR, MIP, ISO) render
  * the reference's arithmetic as written.  background[3] is ignored: a frame's alpha is 1
  * (kernel.cu:213).  VRC normalises by (float)(int)cal_max, TEST, DVR and MIP by the double
  * cal_max. */
@@ -318,6 +359,15 @@ int vr_create_from_nifti(const char* path, const vr_tf_interval* tf, int32_t n_t
 /* Replaces the transfer function (TransferFunction ctor, TransferFunction.cu:8-39);
  * re-classifies on the GPU. */
 int vr_set_transfer_function(vr_ctx* ctx, const vr_tf_interval* tf, int32_t n_tf);
+
+/* VR_MODE_ISO's isovalue (in voxel units, the transfer function's role in that mode) and surface
+ * colour.  A context starts with iso_value = (float)(0.5 * cal_max) and rgb = (1, 1, 1).  VR_EINVAL
+ * for a null context, a null rgb, or a non-finite iso_value or rgb component.  Host state only: the
+ * values travel to the march by value per frame, so a call between queued asynchronous frames needs
+ * no synchronisation and rebuilds nothing.  On a one-process multi-GPU context it applies to every
+ * part; on a one-process-per-GPU group every rank calls it. */
+int vr_set_isosurface(vr_ctx* ctx, float iso_value, const float rgb[3]);
+int vr_get_isosurface(vr_ctx* ctx, float* iso_value, float rgb[3]);
 
 /* deallocateDeviceMemory (kernel.cu:1072-1093). */
 int vr_destroy(vr_ctx* ctx);

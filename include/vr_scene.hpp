@@ -165,6 +165,10 @@ public:
         const std::vector<vr_tf_interval> iv = intervals(tf);
         check(vr_set_transfer_function(ctx_, iv.data(), (int32_t)iv.size()), "vr_set_transfer_function");
     }
+    // VR_MODE_ISO: the isovalue (voxel units) and the surface colour
+    void set_isosurface(float iso_value, const float (&rgb)[3]) {
+        check(vr_set_isosurface(ctx_, iso_value, rgb), "vr_set_isosurface");
+    }
     vr_ctx* handle() const { return ctx_; }
 
     static std::vector<vr_tf_interval> intervals(const TransferFunction& tf) {

@@ -222,6 +222,11 @@ struct vr_ctx {
     vr::DevBuf mip_bound;
     bool mip_valid = false;
     float mip_vol_bound = 0.0f;
+    // VR_MODE_ISO (vr_iso.hip): the isovalue in voxel units (create: half of cal_max) and the surface
+    // colour (vr_set_isosurface); host state only -- the march gets them by value per launch and reads
+    // mip_bound
+    float iso_value = 0.0f;
+    float iso_rgb[3] = {1.0f, 1.0f, 1.0f};
     // TEST: a voxel on the volume's faces is not class 0 (test_faces_kernel; 1 until classified)
     vr::DevBuf faces_flag;
     int32_t test_faces_dirty = 1;

@@ -6,7 +6,8 @@
 //   cls_vrc    uint8 class per voxel for VRC      (TF of max(0,v)/(float)(int)cal_max)
 //   cls_test   uint8 class per voxel for TEST     (TF of (float)(v/cal_max)), built on first use
 //   dvr_*      VR_MODE_DVR: byte copy of the volume, cell min/max and bits, TF segments, built on first use
-//   mip_bound  VR_MODE_MIP: the cells' upper bounds (with DVR's byte copy and cell min/max), built on first use
+//   mip_bound  VR_MODE_MIP / VR_MODE_ISO: the cells' upper bounds (with DVR's byte copy and cell min/max), built on
+//              first use
 //   maps       3 x 2^D int32 leaf -> voxel maps (the octree leaf grid in closed form)
 //   occ        macro-cell occupancy bitmask over the leaf grid (ESS)
 //   tf_rgba    class colours; tf_lohi interval bounds
@@ -74,6 +75,9 @@ hipError_t launch_dvr_cells(const float2*, int64_t, const float*, const float4*,
 hipError_t launch_mip_march(const TestFrame&, const MipFrame&, const WorkTile*, int, const void*, bool, const float*,
                             float4*, hipStream_t);
 hipError_t launch_mip_bounds(const float2*, int64_t, float*, hipStream_t);
+hipError_t launch_iso_march(const TestFrame&, const IsoFrame&, const WorkTile*, int, const void*, bool, const float*,
+                            float4*, hipStream_t);
+static_assert(kIsoRefine == VR_ISO_REFINE, "vr_device.h and vr_api.h disagree on the refinement rounds");
 hipError_t launch_assemble(int, int, int, int, int, int, const float4*, float4*, int, hipStream_t);
 hipError_t launch_assemble_list(int, int, int, int, const int32_t*, const float4*, float4, float4*, int, hipStream_t,
                                 int n_frames = 1);
@@ -601,6 +605,7 @@ vr_ctx* create_common(const float* voxels, bool on_device, int64_t d1, int64_t d
     c->d[0] = d1; c->d[1] = d2; c->d[2] = d3;
     c->cal_max = cal_max;
     c->max_intensity = (int)cal_max;   // kernel.cu:1151 passes double cal_max as int max_intensity
+    c->iso_value = (float)(0.5 * cal_max);
     set_tf(c.get(), tf, n_tf);
     c->oct.build(d1, d2, d3);
     const int D = (int)c->oct.maximum_depth;
@@ -801,8 +806,8 @@ WorkCache* frame_list(vr_ctx* c, const vr_params* p, const vr_camera* cam, const
 #ifndef VR_TEST_AXIS_COLUMN_DEAL
 #define VR_TEST_AXIS_COLUMN_DEAL 0
 #endif
-    // (DVR and MIP frames: one general march for every view, its volume read like the corner volume)
-    const int deal = (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP ||
+    // (DVR, MIP and ISO frames: one general march for every view, its volume read like the corner volume)
+    const int deal = (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO ||
                       (p->mode == VR_MODE_TEST && (VR_TEST_AXIS_COLUMN_DEAL || make_test(c, p, cam).axt < 0))) ? 1 : 0;
     std::vector<uint32_t> key = {(uint32_t)W, (uint32_t)H, (uint32_t)tx0, (uint32_t)tx1, (uint32_t)ty0, (uint32_t)ty1,
                                  (uint32_t)ma, (uint32_t)deal};
@@ -858,8 +863,8 @@ int hull_edges(const vr_ctx* c, const vr_params* p, const vr_camera* cam, float 
 // nothing can be visible, 2 when no claim can be made (TEST mode, opaque TF(0), a corner behind a
 // conic camera, a NaN camera), 1 with the points in xy.
 int project_box(const vr_ctx* c, const vr_params* p, const vr_camera* cam, double xy[8][2]) {
-    // (DVR, MIP: TEST's positions and in-volume test)
-    if (p->mode == VR_MODE_TEST || p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP)
+    // (DVR, MIP, ISO: TEST's positions and in-volume test)
+    if (p->mode == VR_MODE_TEST || p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO)
         return project_box_test(c, p, cam, xy);
     if (p->mode != VR_MODE_VRC || !c->zero_transparent) return 2;
     double lo[3], hi[3];
@@ -901,9 +906,9 @@ int project_box(const vr_ctx* c, const vr_params* p, const vr_camera* cam, doubl
 // transparent an exact no-op of either blend.  So a ray whose line misses the dataset box [0, d]^3
 // is exactly the background: the box's 8 corners mapped back to (x, y) through M^-1 (double
 // precision; the float matrices' rounding is far inside the 2-pixel margin visible_rect adds).
-// MIP frames: a ray without an in-volume sample is the background by definition, whatever TF(0) is.
+// MIP and ISO frames: a ray without an in-volume sample is the background by definition, whatever TF(0) is.
 int project_box_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam, double xy[8][2]) {
-    if (!c->zero_transparent && p->mode != VR_MODE_MIP) return 2;
+    if (!c->zero_transparent && p->mode != VR_MODE_MIP && p->mode != VR_MODE_ISO) return 2;
     CameraState cs;
     cs.pos = {cam->pos[0], cam->pos[1], cam->pos[2]};
     cs.up = {cam->up[0], cam->up[1], cam->up[2]};
@@ -1155,7 +1160,8 @@ std::vector<int32_t> visible_tiles_uncached(const vr_ctx* c, const vr_params* p,
 void check_params(const vr_params* p) {
     if (!p || p->width <= 0 || p->height <= 0 || p->samples_per_ray <= 0 || p->width > 65535 || p->height > 65535)
         throw Error(VR_EINVAL, "vr_params: bad width/height/samples_per_ray");
-    if (p->mode != VR_MODE_VRC && p->mode != VR_MODE_TEST && p->mode != VR_MODE_DVR && p->mode != VR_MODE_MIP)
+    if (p->mode != VR_MODE_VRC && p->mode != VR_MODE_TEST && p->mode != VR_MODE_DVR && p->mode != VR_MODE_MIP &&
+        p->mode != VR_MODE_ISO)
         throw Error(VR_EINVAL, "vr_params: unknown mode");
     if (p->flags & ~(VR_FLAG_ESS | VR_FLAG_ERT | VR_FLAG_SHADE | VR_FLAG_CONIC))
         throw Error(VR_EINVAL, "vr_params: unknown flags");
@@ -1326,8 +1332,8 @@ TestFrame make_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam) {
     f.d1 = c->d[0]; f.d2 = c->d[1]; f.d3 = c->d[2];
     f.total = c->d[0] * c->d[1] * c->d[2];
     f.fd1 = (float)c->d[0]; f.fd2 = (float)c->d[1]; f.fd3 = (float)c->d[2];
-    // (MIP: samples outside the volume take no part, so the clip and the culls hold for any TF)
-    f.zero_transparent = (c->zero_transparent || p->mode == VR_MODE_MIP) ? 1 : 0;
+    // (MIP, ISO: samples outside the volume take no part, so the clip and the culls hold for any TF)
+    f.zero_transparent = (c->zero_transparent || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO) ? 1 : 0;
     f.cls0 = c->cls0_test;
     f.idx64 = (f.total + f.d2 * f.d3 + f.d3 + 1) >= ((int64_t)1 << 31) ? 1 : 0;
     f.tcb = c->tcb;
@@ -1612,7 +1618,7 @@ void ensure_dvr(vr_ctx* c) {
     }
 }
 
-// VR_MODE_MIP's lazy state: ensure_dvr_volume and, on the first MIP frame, the cells' upper bounds
+// VR_MODE_MIP's and VR_MODE_ISO's lazy state: ensure_dvr_volume and, on the first frame of either, the cells' upper bounds
 // (mip_bounds_kernel) with their maximum, the volume-wide bound of the ERT stop.  No TF table, no
 // cell bits.  (Host-synchronised like ensure_dvr: a batch's other streams launch after it.)
 void ensure_mip(vr_ctx* c) {
@@ -1783,9 +1789,9 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
                                    c->cdist_p, gtab, gtab_out, c->count_ptr));
         if (gtab_out) c->axtab[c->stream].key = std::move(pub_key);   // valid for later launches on this stream
     } else {
-        const bool dvr = p->mode == VR_MODE_DVR, mip = p->mode == VR_MODE_MIP;
+        const bool dvr = p->mode == VR_MODE_DVR, mip = p->mode == VR_MODE_MIP, iso = p->mode == VR_MODE_ISO;
         if (dvr) ensure_dvr(c);
-        else if (mip) ensure_mip(c);
+        else if (mip || iso) ensure_mip(c);   // (ISO reads MIP's bounds: a context that renders both builds them once)
         else if (!c->cls_test_valid) classify(c, true);
         TestFrame f = make_test(c, p, cam);
         f.out_tiles = out_tiles; f.tile_w = tile_w; f.tile_h = tile_h; f.n_work = wc->n_work; f.out_rgb = out_rgb;
@@ -1831,6 +1837,23 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             g.vol_bytes = (int32_t)(u8 ? n + 16 : n * 4);   // (the byte copy: a dword at the last voxel stays inside)
             g.bound_bytes = (int32_t)((int64_t)f.tnc[0] * f.tnc[1] * f.tnc[2] * 4);   // (<= 2^18 cells)
             hip_check(launch_mip_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8,
+                                       c->mip_bound.as<float>(), out, c->stream));
+        } else if (iso) {
+            // the ISO march: MIP's frame and bounds, plus the isovalue, the colour and the Phong
+            // coefficients by value (vr_set_isosurface between queued frames touches no device state)
+            const int64_t n = c->d[0] * c->d[1] * c->d[2];
+            const bool u8 = c->dvr_u8_state == 1;
+            f.axt = -1;
+            f.tcb = c->dvr_tcb;
+            for (int a = 0; a < 3; ++a) f.tnc[a] = c->dvr_tnc[a];
+            IsoFrame g;
+            std::memset(&g, 0, sizeof g);
+            g.iso = c->iso_value;
+            for (int a = 0; a < 3; ++a) g.rgb[a] = c->iso_rgb[a];
+            g.ka = p->shade_ambient; g.kd = p->shade_diffuse; g.ks = p->shade_specular; g.shininess = p->shade_shininess;
+            g.vol_bytes = (int32_t)(u8 ? n + 16 : n * 4);   // (the byte copy: a dword at the last voxel stays inside)
+            g.bound_bytes = (int32_t)((int64_t)f.tnc[0] * f.tnc[1] * f.tnc[2] * 4);   // (<= 2^18 cells)
+            hip_check(launch_iso_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8,
                                        c->mip_bound.as<float>(), out, c->stream));
         } else {
         // axis views: the march axis's tables built here once per view and staged by every workgroup
@@ -2162,6 +2185,31 @@ int vr_set_transfer_function(vr_ctx* c, const vr_tf_interval* tf, int32_t n_tf) 
         }, &a);
         return VR_OK;
     });
+}
+
+// VR_MODE_ISO's isovalue (voxel units) and surface colour: host state only, passed to the march by
+// value per launch (IsoFrame), so nothing is rebuilt and queued frames keep the values they were
+// launched with.
+int vr_set_isosurface(vr_ctx* c, float iso_value, const float rgb[3]) {
+    if (!c || !rgb || !std::isfinite(iso_value)) return VR_EINVAL;
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(rgb[a])) return VR_EINVAL;
+    return guard([&] {
+        struct A { float iso; const float* rgb; } a{iso_value, rgb};
+        group_for_each(c, [](vr_ctx* pc, void* p) {
+            const A* x = static_cast<const A*>(p);
+            pc->iso_value = x->iso;
+            for (int i = 0; i < 3; ++i) pc->iso_rgb[i] = x->rgb[i];
+        }, &a);
+        return VR_OK;
+    });
+}
+
+int vr_get_isosurface(vr_ctx* c, float* iso_value, float rgb[3]) {
+    if (!c || !iso_value || !rgb) return VR_EINVAL;
+    *iso_value = c->iso_value;
+    for (int a = 0; a < 3; ++a) rgb[a] = c->iso_rgb[a];
+    return VR_OK;
 }
 
 int vr_destroy(vr_ctx* c) {
@@ -2595,7 +2643,8 @@ int vr_assemble_tiles(vr_ctx* c, int32_t W, int32_t H, int32_t tile_w, int32_t t
 
 int vr_count_samples(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64_t* n_in) {
     if (!c || !cam || !n_in) return VR_EINVAL;
-    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP)) return VR_EINVAL;   // (the counting passes cover VRC and TEST)
+    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO))
+        return VR_EINVAL;   // (the counting passes cover VRC and TEST)
     return guard([&] {
         check_params(p);
         set_device(c);
@@ -2619,8 +2668,8 @@ int vr_count_samples(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64
 // axis_columns_plan's scope), and the tests that pin these counts pin that definition.
 int vr_count_work(vr_ctx* c, const vr_params* p, const vr_camera* cam, vr_work_count* out) {
     if (!c || !cam || !out) return VR_EINVAL;
-    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP))
-        return VR_EINVAL;   // (no counting instantiation of the DVR and MIP marches)
+    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO))
+        return VR_EINVAL;   // (no counting instantiation of the DVR, MIP and ISO marches)
     return guard([&] {
         check_params(p);
         set_device(c);

@@ -190,6 +190,18 @@ struct MipFrame {
     int32_t reserved;
 };
 
+// The ISO march (vr_iso.hip) takes the same from a TestFrame as the MIP march, reads MIP's cell bounds
+// against a fixed threshold, and adds -- by value per launch, so vr_set_isosurface between queued
+// frames needs no synchronisation:
+constexpr int kIsoRefine = 6;   // bisection rounds (VR_ISO_REFINE)
+struct IsoFrame {
+    float iso;                  // the isovalue, in voxel units
+    float rgb[3];               // the surface colour
+    float ka, kd, ks, shininess;   // vr_params.shade_*
+    int32_t vol_bytes;          // bytes of the array the corner gathers read (their buffer bound)
+    int32_t bound_bytes;        // bytes of the cells' upper bounds (one float per cell)
+};
+
 // TransferFunction::getMaterial (TransferFunction.cu:46-55): last closed interval containing v, else 0
 __device__ __forceinline__ int tf_class(const float* lo, const float* hi, int n, float v) {
     int r = 0;

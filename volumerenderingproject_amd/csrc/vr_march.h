@@ -1,5 +1,5 @@
 // vr_march.h -- device helpers shared by the march kernels (vr_kernels.hip: VRC and the setup
-// kernels; vr_test.hip: TEST; vr_dvr.hip: DVR; vr_mip.hip: MIP).  Internal, not the ABI.
+// kernels; vr_test.hip: TEST; vr_dvr.hip: DVR; vr_mip.hip: MIP; vr_iso.hip: ISO).  Internal, not the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -272,6 +272,27 @@ __device__ __forceinline__ float lerp1(float a, float b, float w) {
 #pragma clang fp contract(off)
     const float u = 1.0f - w;
     return a * u + b * w;
+}
+
+// Headlight Phong at a sample (oracle or_shade: same operations, same order):
+// d = max(0, N.L), spec = ks * d^shininess, rgb' = rgb * (ka + kd d) + spec; flat (w = 0): d = 1.
+__device__ __forceinline__ void shade_normal(const float4 nv, const float L[3], float ka, float kd, float ks,
+                                             float shin, float& r, float& g, float& b) {
+    float d = 1.0f, spec = 0.0f;
+    if (nv.w != 0.0f) {
+        const float ndl = (nv.x * L[0] + nv.y * L[1]) + nv.z * L[2];
+        d = ndl > 0.0f ? ndl : 0.0f;
+        // d^shininess as exp2(shininess * log2 d) on the hardware transcendentals (d > 0); d = 0 gives 0.
+        // v_log_f32 reads a denormal d as 0 (-inf, and 0 * -inf = NaN at shininess 0): such a d is
+        // scaled into the normal range first, log2 d = log2(d 2^32) - 32 (a normal d is untouched)
+        const bool den = d < 0x1p-126f;
+        const float l2 = __builtin_amdgcn_logf(den ? d * 0x1p32f : d) - (den ? 32.0f : 0.0f);
+        spec = d > 0.0f ? ks * __builtin_amdgcn_exp2f(shin * l2) : (shin == 0.0f ? ks : 0.0f);
+    }
+    const float k = ka + kd * d;
+    r = r * k + spec;
+    g = g * k + spec;
+    b = b * k + spec;
 }
 
 // Whole TEST, DVR and MIP frames: work tiles off the dataset box's projection (vr_api.cpp project_box_test) are

@@ -23,6 +23,8 @@ VR_MODE_VRC = 1
 VR_MODE_TEST = 5
 VR_MODE_DVR = 6       # trilinear sample of the scalar field, then TF classification
 VR_MODE_MIP = 7       # maximum-intensity projection of the same trilinear field (no TF)
+VR_MODE_ISO = 8       # shaded first-hit isosurface of the same trilinear field (set_isosurface; no TF)
+VR_ISO_REFINE = 6     # its bisection rounds
 VR_FLAG_ESS = 1
 VR_FLAG_ERT = 2
 VR_FLAG_SHADE = 8
@@ -43,7 +45,7 @@ EXPORTED = [
     "vr_assemble_tile_slots_multi", "vr_options_default", "vr_create_ex", "vr_get_options", "vr_set_options",
     "vr_create_multi", "vr_comm_unique_id", "vr_create_rank", "vr_group_info", "vr_group_tiles", "vr_render_png",
     "vr_render_batch", "vr_create_multi_ex", "vr_group_timing_read", "vr_count_work", "vr_group_traffic_read",
-    "vr_axis_columns_plan", "vr_tf_segments",
+    "vr_axis_columns_plan", "vr_tf_segments", "vr_set_isosurface", "vr_get_isosurface",
 ]
 VR_COMM_ID_BYTES = 128
 VR_TRANSPORT_NONE, VR_TRANSPORT_RCCL, VR_TRANSPORT_PEER_COPY = 0, 1, 2
@@ -169,6 +171,8 @@ def lib():
         "vr_group_tiles": ([vp, C.c_int32, P(C.c_int32), C.c_int32, P(C.c_int32)], C.c_int),
         "vr_set_options": ([vp, P(Options)], C.c_int),
         "vr_set_transfer_function": ([vp, P(TFInterval), C.c_int32], C.c_int),
+        "vr_set_isosurface": ([vp, C.c_float, P(C.c_float)], C.c_int),
+        "vr_get_isosurface": ([vp, P(C.c_float), P(C.c_float)], C.c_int),
         "vr_destroy": ([vp], C.c_int),
         "vr_render": ([vp, P(RenderParams), P(Camera), vp, C.c_int32], C.c_int),
         "vr_render_tiles": ([vp, P(RenderParams), P(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp,
@@ -467,6 +471,18 @@ class VolumeRenderer:
     def set_transfer_function(self, tf):
         self._tf = _tf_array(tf)
         _check(lib().vr_set_transfer_function(self._ctx, self._tf, len(tf)), "vr_set_transfer_function")
+
+    def set_isosurface(self, iso_value, rgb=(1.0, 1.0, 1.0)):
+        """VR_MODE_ISO's isovalue (voxel units) and surface colour; host state, nothing is rebuilt."""
+        c = (C.c_float * 3)(*[float(v) for v in rgb])
+        _check(lib().vr_set_isosurface(self._ctx, float(iso_value), c), "vr_set_isosurface")
+
+    @property
+    def isosurface(self):
+        """(iso_value, (r, g, b)) as the context holds them (float32)."""
+        iso, c = C.c_float(), (C.c_float * 3)()
+        _check(lib().vr_get_isosurface(self._ctx, C.byref(iso), c), "vr_get_isosurface")
+        return iso.value, (c[0], c[1], c[2])
 
     def render(self, params: RenderParams, camera: Camera) -> np.ndarray:
         """Host frame, shape (W, H, 4), x-major like the reference's screen buffer."""
