@@ -345,25 +345,29 @@ def test_dvr_occ_lds_off(avg152, oracle_mod, W, H, S):
                 assert_bits(b.render(p, cam), fa, (name, fl))
 
 
-# ---- the whole-frame screen cull, DVR and MIP -----------------------------------------------------------
+# ---- the whole-frame screen cull, DVR, MIP and ISO -----------------------------------------------------------
 
 OPAQUE0 = [(0.0, 1.0, (0.1, 0.2, 0.3, 0.05)), (0.3, 0.6, (0.9, 0.5, 0.1, 0.4))]   # test_tf_paths' opaque0
 
 
+FIELD_MODES = {"dvr": DVR, "mip": vr.VR_MODE_MIP, "iso": vr.VR_MODE_ISO}
+ISO_SURFACE = (100.0, (0.9, 0.8, 0.7))   # ISO in the two tests below: set on every context before its first call
+
+
 @pytest.mark.parametrize("mode,tf_name", [("dvr", "default"), ("dvr", "opaque0"), ("mip", "default"),
-                                          ("mip", "opaque0")])
+                                          ("mip", "opaque0"), ("iso", "default"), ("iso", "opaque0")])
 def test_screen_cull_is_exact(avg152, mode, tf_name):
-    """Whole DVR and MIP frames cull the work tiles off the dataset box's projection (rectangle: cull 1;
+    """Whole DVR, MIP and ISO frames cull the work tiles off the dataset box's projection (rectangle: cull 1;
     its hull on general views: cull 2) into background-only workgroups.  160 x 96 is 10 x 6 work tiles:
     hull-culled tiles and more than one background-only workgroup (kBgGroup = 8 tiles each).  Contexts
     with cull 2, 1 and 0 render the same frames bit for bit in every flag combination, and the farm's
     visible tiles keep every 16 x 16 tile with a non-background pixel.  Under a TF whose class of 0 is
-    opaque a DVR frame has no background to cull to -- every tile is returned -- and MIP, which reads no
-    TF, keeps its culls."""
+    opaque a DVR frame has no background to cull to -- every tile is returned -- and MIP and ISO, which
+    read no TF, keep their culls."""
     from test_gpu_test_mode import _orbit_views, z_cameras
     vol, cal = avg152
     W, H, S = 160, 96, 64
-    m = DVR if mode == "dvr" else vr.VR_MODE_MIP
+    m = FIELD_MODES[mode]
     tf = vr.default_transfer_function() if tf_name == "default" else OPAQUE0
     cams = dict(z_cameras(W, H))   # (its "far" is the far camera at (0, 0, 2.5))
     cams.update(_orbit_views(W, H))
@@ -372,6 +376,9 @@ def test_screen_cull_is_exact(avg152, mode, tf_name):
     bg = np.array([0.2, 0.2, 0.2], F)
     rs = [vr.VolumeRenderer(vol, cal, tf=tf, device=0, options=vr.default_options(cull=c)) for c in (2, 1, 0)]
     try:
+        if mode == "iso":
+            for r in rs:
+                r.set_isosurface(*ISO_SURFACE)
         n_vis, n_rect = {}, {}
         for name, cam in cams.items():
             for fl in (0, E, T, E | T):
@@ -402,25 +409,30 @@ def test_screen_cull_is_exact(avg152, mode, tf_name):
 # ---- lazy state built inside a batch ------------------------------------------------------------------
 
 @pytest.mark.parametrize("frames_in_flight", [0, 1, 3])
-@pytest.mark.parametrize("mode", ["dvr", "mip"])
+@pytest.mark.parametrize("mode", ["dvr", "mip", "iso"])
 def test_first_call_is_a_batch(avg152, oracle_mod, mode, frames_in_flight):
     """ensure_dvr / ensure_mip build the byte copy, the cell min/max, the segments and the bounds with
     the first frame of a mode and end with a host synchronisation of the context's current stream;
     vr_render_batch forks its frames over up to four streams.  A context whose first call is a batch
     gives the frames of five single renders on another context, bit for bit; so does a batch right
-    after a TF change (DVR: the frames of a context created with that TF; MIP: the same frames)."""
+    after a TF change (DVR: the frames of a context created with that TF; MIP and ISO: the same frames).
+    ISO builds through ensure_mip too; its surface is host state, set before the batch."""
     vol, cal = avg152
     W, H, S = 64, 48, 64
-    m = DVR if mode == "dvr" else vr.VR_MODE_MIP
+    m = FIELD_MODES[mode]
     p = vr.default_params(W, H, S, mode=m, flags=E)
     cams = [camera_pair(oracle_mod, n, W, H)[0] for n in ("default", "reset", "inside", "x", "-y")]
     tf2 = seeded_tf(17, 17)
     for dvr_volume in (0, 1):
         with vr.VolumeRenderer(vol, cal, device=0, options=vr.default_options(dvr_volume=dvr_volume)) as single:
+            if mode == "iso":
+                single.set_isosurface(*ISO_SURFACE)
             want = [single.render(p, c) for c in cams]
         assert any(np.any(w[..., :3] != w[0, 0, :3]) for w in want)
         opts = vr.default_options(dvr_volume=dvr_volume, frames_in_flight=frames_in_flight)
         with vr.VolumeRenderer(vol, cal, device=0, options=opts) as r:
+            if mode == "iso":
+                r.set_isosurface(*ISO_SURFACE)   # (host state: the batch is still the first call that renders)
             batch = r.render_batch(p, cams)   # the context's first call
             for f in range(len(cams)):
                 assert_bits(batch[f], want[f], (mode, dvr_volume, "first batch", f))

@@ -3,7 +3,8 @@ processInput's formulas, myApp.cu:1105-1112, on both sides), odd frame sizes and
 every compositing mode.  Exact and ESS-only frames are bitwise the oracle's (the reference's
 back-to-front blend, kernel.cu:194-225); ESS + ERT and ERT alone within 1e-4; TEST exact bitwise
 (kernel.cu:72-187).  Covers the general-view paths (padded leaf maps, lazy empty-space tests,
-empty-cell skipping of exact frames) on views no other test picks."""
+empty-cell skipping of exact frames) on views no other test picks.  The same views in DVR, MIP and ISO
+against tests/dvr_ref.py, mip_ref.py and iso_ref.py (test_random_views_field_modes)."""
 import math
 
 import numpy as np
@@ -54,3 +55,57 @@ def test_random_views_match_oracle(avg152, avg152_octree, oracle_mod, seed):
                 assert_bitwise(r.render(vr.default_params(W, H, S, mode=vr.VR_MODE_TEST), cam), tref)
     finally:
         r.close()
+
+
+ISO_RGB, ISO_SHADE = (0.9, 0.8, 0.7), (0.3, 0.7, 0.0, 16.0)   # (ks = 0: the specular term is exact)
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_random_views_field_modes(avg152, oracle_mod, seed):
+    """The three modes of the trilinear field on the same views, against their numpy restatements.  DVR:
+    exact and ESS bitwise, ERT and ESS | ERT within TOL.  MIP and ISO: all four flag combinations
+    bitwise; ISO at iso = 100 (refined surfaces) and at iso = -1 (the first in-volume sample of every
+    ray: the clip).  Every third view again from the float volume (dvr_volume = 1)."""
+    import dvr_ref
+    import iso_ref
+    import mip_ref
+    from test_gpu_params import assert_same
+    vol, cal = avg152
+    O = oracle_mod
+    tf = vr.default_transfer_function()
+    DVR, MIP, ISO = vr.VR_MODE_DVR, vr.VR_MODE_MIP, vr.VR_MODE_ISO
+
+    def params(mode, W, H, S, flags):
+        p = vr.default_params(W, H, S, mode=mode, flags=flags)
+        if mode == ISO:
+            p.shade_ambient, p.shade_diffuse, p.shade_specular, p.shade_shininess = ISO_SHADE
+        return p
+
+    hits = refinable = 0
+    with vr.VolumeRenderer(vol, cal, device=0) as a, \
+            vr.VolumeRenderer(vol, cal, device=0, options=vr.default_options(dvr_volume=1)) as b:
+        for i, (W, H, S, pos, up) in enumerate(random_views(16, seed)):
+            op = O.params(W, H, S)
+            cam = vr.derive_camera(pos, up, op.real_screen_width, op.real_screen_height)
+            ocam = O.camera_derive(pos, up, op.real_screen_width, op.real_screen_height)
+            dref = dvr_ref.render(vol, cal, tf, op, ocam)
+            mref = mip_ref.render(vol, cal, op, ocam)[0]
+            irefs = {}
+            for iso in (100.0, -1.0):
+                irefs[iso], rec = iso_ref.render(vol, op, ocam, iso, ISO_RGB, ISO_SHADE)
+                hits += int(rec["hit"].sum())
+                refinable += int(rec["refinable"].sum())
+            for r in ((a, b) if i % 3 == 0 else (a,)):
+                for flags in (0, E):
+                    assert_same(r.render(params(DVR, W, H, S, flags), cam), dref, (i, "dvr", flags))
+                for flags in (T, E | T):
+                    got = r.render(params(DVR, W, H, S, flags), cam)
+                    assert np.abs(got - dref).max() <= TOL, (i, flags)
+                for flags in (0, E, T, E | T):
+                    assert_same(r.render(params(MIP, W, H, S, flags), cam), mref, (i, "mip", flags))
+                for iso, iref in irefs.items():
+                    r.set_isosurface(iso, ISO_RGB)
+                    for flags in (0, E, T, E | T):
+                        assert_same(r.render(params(ISO, W, H, S, flags), cam), iref, (i, "iso", iso, flags))
+    # the views bite (iso_ref's records over both isovalues: 21223 hit rays and 6403 refinable ones at the least)
+    assert hits >= 2000 and refinable >= 1500, (seed, hits, refinable)

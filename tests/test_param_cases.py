@@ -3,7 +3,9 @@ case draws something and leaves background, the tiny shapes are visible, the spe
 the frame, the closed-form octree equals the literal one where both exist, the DVR restatement
 stays pinned to the oracle off the default viewplane distance, and the same cases draw in VR_MODE_MIP
 (mip_ref): enough in-volume pixels and different maxima, clamped and unclamped pixels at a fractional
-cal_max, the deep shapes, and a volume of subnormals that is not the zero volume."""
+cal_max, the deep shapes, and a volume of subnormals that is not the zero volume.  VR_MODE_ISO
+(iso_ref's record): enough hit rays on every row, refinable and non-refinable hits, the first
+in-volume sample at iso = -1, the thresholds of blob_special(), and the three ranges of len2."""
 import numpy as np
 import pytest
 
@@ -207,6 +209,145 @@ def test_subnormal_volume_is_not_the_zero_volume():
             assert changed >= MIN_PIXELS, (view, mode, changed)
         f, m, hit = ref.mip(Case(view, MIP))
         assert len(np.unique(m[hit])) >= 90 and np.all(m[hit] < F32(2.0 ** -126)), view
+
+
+# ---- VR_MODE_ISO: the cases of tests/test_gpu_params.py, tests/test_gpu_volumes.py are not vacuous.
+# Conditions on iso_ref's record; the floors are round numbers under what the restatement gives.
+
+ISO_SPECIAL, ISO_SUBNORMAL, ISO_SMALL, ISO_DEEP = pc.ISO_SPECIAL, pc.ISO_SUBNORMAL, pc.ISO_SMALL, pc.ISO_DEEP
+
+
+def iso_record(ref, case):
+    frame, rec = ref.iso(case)
+    assert frame is ref.frame(case) and np.all(np.isfinite(frame)) and np.all(frame[..., 3] == 1.0), case.key()
+    return frame, rec
+
+
+def check_iso_hits_first_inside(ref, case, what):
+    """Every in-volume ray hits at its first in-volume sample, and none is refinable (that sample's
+    predecessor is outside the volume): the linear-model clip may not drop it."""
+    frame, rec = iso_record(ref, case)
+    inside = ref.inside(case)
+    hit = rec["hit"]
+    assert np.array_equal(hit, inside.any(axis=2)) and hit.any(), what
+    assert np.array_equal(rec["s_h"][hit], inside.argmax(axis=2)[hit]), what
+    assert not rec["refinable"].any(), what
+    return frame, rec
+
+
+@pytest.mark.parametrize("vpd,scale", pc.VPD)
+def test_iso_vpd_cases_draw(vpd, scale):
+    """iso = 128 on the blob: at least 50 hit rays (52 at (0.0, 0.2) along obl).  With every sample in the
+    camera plane there is no light direction and nothing to refine; with the camera inside the box
+    some view has hits whose predecessor is outside beside hits that are refined."""
+    ref = pc.shared_reference("blob")
+    mixed = False
+    for view in pc.VIEWS:
+        _, rec = iso_record(ref, Case(view, pc.ISO, vpd=vpd, scale=scale))
+        hit = rec["hit"]
+        n, nr = int(hit.sum()), int(rec["refinable"].sum())
+        assert n >= 50, (vpd, scale, view, n)
+        if vpd == 0.0:
+            assert nr == 0 and np.all(rec["d"][hit] == 1.0), (view, nr)
+        mixed |= 0 < nr < n
+        # and at iso = -1: the clip check
+        check_iso_hits_first_inside(ref, Case(view, pc.ISO, vpd=vpd, scale=scale, iso=-1.0), (vpd, scale, view))
+    if (vpd, scale) in ((0.6, 0.3), (-0.5, -0.2)):
+        assert mixed, (vpd, scale)
+
+
+@pytest.mark.parametrize("rsw,rsh", pc.SCREENS)
+def test_iso_screen_cases_draw(rsw, rsh):
+    """At least 70 hits (76 the smallest), all refinable: the blob lies strictly inside the volume."""
+    ref = pc.shared_reference("blob")
+    for view in pc.VIEWS:
+        _, rec = iso_record(ref, Case(view, pc.ISO, rsw=rsw, rsh=rsh))
+        n = int(rec["hit"].sum())
+        assert n >= 70 and np.array_equal(rec["refinable"], rec["hit"]), (rsw, rsh, view, n)
+        check_iso_hits_first_inside(ref, Case(view, pc.ISO, rsw=rsw, rsh=rsh, iso=-1.0), (rsw, rsh, view))
+
+
+@pytest.mark.parametrize("iso", ISO_SPECIAL)
+def test_iso_special_voxels_thresholds(iso):
+    """blob_special() under thresholds from below every voxel to above every one: the cell bounds' margin
+    (max + 2^-20 max(|min|, |max|)) is tried at each, and from 255.5 up a hit lies beside a voxel of 1e30
+    or 3.4e38 -- len2 overflows to +inf, inv = 0, N = (-0, -0, -0), d = 0 on a ray that has a normal."""
+    ref = pc.shared_reference("special")
+    bg = np.array(pc.DEFAULT_BG[:3], F32)
+    for view in ("z", "x", "obl"):
+        case = Case(view, pc.ISO, iso=iso)
+        if iso < 0:
+            check_iso_hits_first_inside(ref, case, (iso, view))
+            continue
+        frame, rec = iso_record(ref, case)
+        hit = rec["hit"]
+        n = int(hit.sum())
+        if iso in (1e-40, 100.0):   # (224 and 220 at the least)
+            assert n >= 200 and np.array_equal(rec["refinable"], hit), (iso, view, n)
+        elif iso in (255.5, 1e30):  # (51 at the least, at 1e30)
+            assert n >= 50, (iso, view, n)
+            assert np.all(rec["has_normal"][hit]) and np.all(rec["d"][hit] == 0.0), (iso, view)
+            assert np.all(rec["N"][hit] == 0.0), (iso, view)
+        else:
+            assert n == 0 and np.all(frame[..., :3] == bg), (iso, view, n)
+
+
+def test_iso_subnormal_volume_has_a_surface_and_no_normal():
+    """blob_subnormal() at 128 * 2^-140: the blob's surface at 128 (hit, s_h and hi are equal: scaling by
+    a power of two commutes with every lerp down there, no product rounds), but len2 -- squares of
+    gradients below 2^-132 -- underflows to 0 on every hit: no normal, d = 1.  Not the zero volume's frame."""
+    ref, blob = pc.shared_reference("subnormal"), pc.shared_reference("blob")
+    zero = pc.Reference(np.zeros_like(ref.vol), pc.SUBNORMAL_CAL, literal=False)
+    for view in ("z", "x", "obl"):
+        case = Case(view, pc.ISO, iso=ISO_SUBNORMAL)
+        frame, rec = iso_record(ref, case)
+        _, want = iso_record(blob, Case(view, pc.ISO))
+        hit = rec["hit"]
+        assert int(hit.sum()) >= 200, view
+        for k in ("hit", "s_h", "hi"):
+            assert np.array_equal(rec[k], want[k]), (view, k)
+        assert not rec["has_normal"][hit].any() and np.all(rec["d"][hit] == 1.0), view
+        changed = int(np.any(frame != zero.frame(case), axis=-1).sum())
+        assert changed >= MIN_PIXELS, (view, changed)
+
+
+def test_iso_small_volume_normals_come_from_subnormal_len2():
+    """blob_small() at 128 * 2^-72: the blob's surface again, and every hit has a normal although len2 is
+    a subnormal: few bits are left of it, so N = -g / sqrt(len2) is not the blob's N on most rays (equal
+    on 5 of 224 along z, 10 of 322 along obl).  A device that flushed len2 (no normal, d = 1) or took
+    the square root as if its input were normal cannot produce this frame."""
+    ref, blob = pc.shared_reference("small"), pc.shared_reference("blob")
+    v = ref.vol
+    nz = v[v != 0]
+    assert np.all(nz >= F32(2.0 ** -126)) and np.array_equal(v.astype(np.float64) * 2.0 ** 72, pc.blob())
+    for view in ("z", "x", "obl"):
+        case = Case(view, pc.ISO, iso=ISO_SMALL)
+        frame, rec = iso_record(ref, case)
+        plain_frame, want = iso_record(blob, Case(view, pc.ISO))
+        hit = rec["hit"]
+        n = int(hit.sum())
+        assert n >= 200, (view, n)
+        for k in ("hit", "s_h", "hi"):
+            assert np.array_equal(rec[k], want[k]), (view, k)
+        assert np.all(rec["has_normal"][hit]), view
+        differ = int(np.any(rec["N"][hit] != want["N"][hit], axis=-1).sum())
+        assert 2 * differ > n, (view, differ, n)
+        assert pc.non_background(frame) >= MIN_PIXELS and not np.array_equal(frame, plain_frame), view
+
+
+@pytest.mark.parametrize("name", list(pc.DEEP))
+def test_deep_shapes_in_iso(name):
+    """iso = 112 on the needles over deep_volume_cases: deep_x 17 / 1 / 17 / 0 / 8 hits, deep_z 1 / 16 /
+    14 / 0 / 6 (z, x, y_back, obl at 1.2, obl at 0.02)."""
+    ref = pc.shared_reference(name)
+    assert float(np.median(ref.vol)) == ISO_DEEP
+    for case in pc.deep_volume_cases(pc.ISO, iso=ISO_DEEP):
+        _, rec = iso_record(ref, case)
+        n = int(rec["hit"].sum())
+        if case.view == "obl" and case.rsw == 1.2:
+            assert n == 0, (name, n)
+        else:
+            assert n > 0, (name, case.view, case.rsw, n)
 
 
 # ---- the shading stage (VR_FLAG_SHADE): the cases of tests/test_gpu_shade.py are not vacuous ----
