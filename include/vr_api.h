@@ -239,7 +239,14 @@ typedef struct {
                                   (four corner-row gathers per sample).  Exact frames bitwise the
                                   same in every mode; front to back (VR_FLAG_ERT) with <= 4 intervals,
                                   modes 0 and 3 read a 16-KB plane table instead of the TF and agree
-                                  with modes 1 and 2 within the ERT tolerance                       */
+                                  with modes 1 and 2 within the ERT tolerance.  The plane table is
+                                  taken only while the march's other LDS -- 16 B per TF interval, the
+                                  occupancy bits under VR_FLAG_ESS, 16 B per sample of [-4, S + 4) and,
+                                  mode 3, 4 B per voxel row of each axis -- leaves it room within
+                                  32 KB: 16 (S + 8) <= 16384 less those tables, i.e. samples_per_ray
+                                  up to about 1000 (1011 at 4 intervals and 16 B of occupancy bits;
+                                  fewer in mode 3).  Longer rays read the TF in every mode, and their
+                                  front-to-back frames are then bitwise the same in all four         */
     int32_t leaf_columns;      /* axis-aligned ESS marches read the empty-cell mask of the ray's own leaf
                                   column (1, default, up to 2048 leaves per axis) instead of its 4 x 4-
                                   leaf cell column (0).  Device memory per classification (every TF
