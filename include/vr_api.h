@@ -117,6 +117,44 @@ extern "C" {
                               and vr_visible_tiles as for VR_MODE_MIP.  The transfer function plays no
                               part.                                                                     */
 #define VR_ISO_REFINE 6    /* VR_MODE_ISO: bisection rounds between samples s_h - 1 and s_h             */
+#define VR_MODE_SDVR 9     /* gradient-shaded VR_MODE_DVR: direct volume rendering of the same trilinear field
+                              with every non-transparent in-volume sample lit (no reference mode).  All
+                              arithmetic is float32, every operation rounded on its own (no contraction,
+                              IEEE division and square root).
+                              1. Samples: VR_MODE_DVR's, operation for operation: the positions p(x, y, s),
+                              the in-volume test 0 <= p_a < d_a, the value v, and the class and colour
+                              (r, g, b, a) = TF((float)((double)v / cal_max)).  A sample outside the volume
+                              is TF((float)(0.0f / cal_max)), unshaded.
+                              2. Shaded samples: those in the volume with a != 0.0f.  Every other sample
+                              keeps its DVR colour (an alpha-0 sample stays the exact no-op of both blends
+                              that empty-space skipping relies on).
+                              3. Gradient at the sample's own position p (VR_MODE_ISO's step 4 with p* = p),
+                              per axis a: q+ = min(p_a + 1.0f, (float)(d_a - 1)), q- = max(p_a - 1.0f, 0.0f),
+                              v+ / v- the field value with coordinate a replaced by q+ / q-, span = q+ - q-,
+                              g_a = span > 0 ? (v+ - v-) / span : 0; len2 = (gx*gx + gy*gy) + gz*gz; if
+                              len2 > 0: inv = 1.0f / sqrtf(len2) and N = (-gx*inv, -gy*inv, -gz*inv),
+                              otherwise there is no normal.
+                              4. Light (VR_MODE_ISO's step 5), once per ray:
+                              e = p(x, y, S > 1 ? S - 1 : 0) - p(x, y, 0), n2 = (ex*ex + ey*ey) + ez*ez; if
+                              n2 > 0: L = -e * (1.0f / sqrtf(n2)), otherwise there is no light direction.
+                              5. Two-sided lighting: ndl = (Nx*Lx + Ny*Ly) + Nz*Lz; if ndl < 0, N is negated
+                              (exact) before the law, so its d = |ndl|: a compositing march sees both sides
+                              of every material shell.
+                              6. Colour, VR_FLAG_SHADE's law with ka, kd, ks, shininess = vr_params.shade_*
+                              (read without the flag): d = max(ndl, 0), spec = d > 0 ? ks * d^shininess :
+                              (shininess == 0 ? ks : 0), d^shininess as exp2(shininess * log2 d) on the
+                              hardware transcendentals; without a normal or a light d = 1, spec = 0.  Each
+                              channel is c' = c * (ka + kd*d) + spec, unclamped; alpha is unchanged.
+                              7. Blend: VR_MODE_DVR's two blends with c' in place of c: back to front
+                              f = f*(1 - a) + c'*a; front to back with VR_FLAG_ERT, within the ERT
+                              tolerance.  Frame alpha is 1.
+                              8. VR_FLAG_ESS is exact (bitwise the exact frame); VR_FLAG_ERT as in
+                              VR_MODE_DVR.  VR_FLAG_SHADE / VR_FLAG_CONIC are VR_EINVAL (the mode always
+                              shades).  cal_max must be finite and > 0 (VR_EINVAL at render); the size
+                              limit is VR_MODE_DVR's (VR_ERANGE).  vr_count_samples / vr_count_marched /
+                              vr_count_work: VR_EINVAL; vr_axis_columns_plan reports no column path; culling
+                              and vr_visible_tiles as for VR_MODE_DVR.  The mode reads VR_MODE_DVR's
+                              context state and builds none of its own; vr_set_isosurface plays no part. */
 
 /* ---- render flags -------------------------------------------------------------------------- */
 #define VR_FLAG_ESS 1      /* empty-space skipping (bitwise exact: skips only alpha-0 samples)  */

@@ -208,7 +208,8 @@ struct vr_ctx {
     // (cleared when the classes change)
     mutable std::map<std::vector<uint32_t>, std::vector<int32_t>> vis_cache;
     bool cls_test_valid = false;
-    // VR_MODE_DVR (vr_dvr.hip), built on the first DVR frame: the byte copy of the volume (dvr_u8_state
+    // VR_MODE_DVR (vr_dvr.hip) and VR_MODE_SDVR (vr_sdvr.hip, which adds nothing), built on the first
+    // frame of either: the byte copy of the volume (dvr_u8_state
     // 0 = not tried, 1 = built and lossless, 2 = the volume is not bytes / the option forbids it), the
     // min/max of the cells (2^dvr_tcb voxels per axis), and -- rebuilt when the TF changes (dvr_tf_valid)
     // -- the TF's segments (starts, colours) and the cells' occupancy bits

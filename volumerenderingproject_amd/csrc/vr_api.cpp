@@ -5,7 +5,7 @@
 //   vol        float32 volume, x-major (kept for re-classification when the TF changes)
 //   cls_vrc    uint8 class per voxel for VRC      (TF of max(0,v)/(float)(int)cal_max)
 //   cls_test   uint8 class per voxel for TEST     (TF of (float)(v/cal_max)), built on first use
-//   dvr_*      VR_MODE_DVR: byte copy of the volume, cell min/max and bits, TF segments, built on first use
+//   dvr_*      VR_MODE_DVR / VR_MODE_SDVR: byte copy of the volume, cell min/max and bits, TF segments, built on first use
 //   mip_bound  VR_MODE_MIP / VR_MODE_ISO: the cells' upper bounds (with DVR's byte copy and cell min/max), built on
 //              first use
 //   maps       3 x 2^D int32 leaf -> voxel maps (the octree leaf grid in closed form)
@@ -77,6 +77,8 @@ hipError_t launch_mip_march(const TestFrame&, const MipFrame&, const WorkTile*, 
 hipError_t launch_mip_bounds(const float2*, int64_t, float*, hipStream_t);
 hipError_t launch_iso_march(const TestFrame&, const IsoFrame&, const WorkTile*, int, const void*, bool, const float*,
                             float4*, hipStream_t);
+hipError_t launch_sdvr_march(const TestFrame&, const DvrFrame&, const SdvrFrame&, const WorkTile*, int, const void*, bool,
+                             const float*, const float4*, const uint32_t*, float4*, hipStream_t);
 static_assert(kIsoRefine == VR_ISO_REFINE, "vr_device.h and vr_api.h disagree on the refinement rounds");
 hipError_t launch_assemble(int, int, int, int, int, int, const float4*, float4*, int, hipStream_t);
 hipError_t launch_assemble_list(int, int, int, int, const int32_t*, const float4*, float4, float4*, int, hipStream_t,
@@ -806,8 +808,9 @@ WorkCache* frame_list(vr_ctx* c, const vr_params* p, const vr_camera* cam, const
 #ifndef VR_TEST_AXIS_COLUMN_DEAL
 #define VR_TEST_AXIS_COLUMN_DEAL 0
 #endif
-    // (DVR, MIP and ISO frames: one general march for every view, its volume read like the corner volume)
+    // (DVR, SDVR, MIP and ISO frames: one general march for every view, its volume read like the corner volume)
     const int deal = (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO ||
+                      p->mode == VR_MODE_SDVR ||
                       (p->mode == VR_MODE_TEST && (VR_TEST_AXIS_COLUMN_DEAL || make_test(c, p, cam).axt < 0))) ? 1 : 0;
     std::vector<uint32_t> key = {(uint32_t)W, (uint32_t)H, (uint32_t)tx0, (uint32_t)tx1, (uint32_t)ty0, (uint32_t)ty1,
                                  (uint32_t)ma, (uint32_t)deal};
@@ -863,8 +866,9 @@ int hull_edges(const vr_ctx* c, const vr_params* p, const vr_camera* cam, float 
 // nothing can be visible, 2 when no claim can be made (TEST mode, opaque TF(0), a corner behind a
 // conic camera, a NaN camera), 1 with the points in xy.
 int project_box(const vr_ctx* c, const vr_params* p, const vr_camera* cam, double xy[8][2]) {
-    // (DVR, MIP, ISO: TEST's positions and in-volume test)
-    if (p->mode == VR_MODE_TEST || p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO)
+    // (DVR, SDVR, MIP, ISO: TEST's positions and in-volume test)
+    if (p->mode == VR_MODE_TEST || p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO ||
+        p->mode == VR_MODE_SDVR)
         return project_box_test(c, p, cam, xy);
     if (p->mode != VR_MODE_VRC || !c->zero_transparent) return 2;
     double lo[3], hi[3];
@@ -1161,7 +1165,7 @@ void check_params(const vr_params* p) {
     if (!p || p->width <= 0 || p->height <= 0 || p->samples_per_ray <= 0 || p->width > 65535 || p->height > 65535)
         throw Error(VR_EINVAL, "vr_params: bad width/height/samples_per_ray");
     if (p->mode != VR_MODE_VRC && p->mode != VR_MODE_TEST && p->mode != VR_MODE_DVR && p->mode != VR_MODE_MIP &&
-        p->mode != VR_MODE_ISO)
+        p->mode != VR_MODE_ISO && p->mode != VR_MODE_SDVR)
         throw Error(VR_EINVAL, "vr_params: unknown mode");
     if (p->flags & ~(VR_FLAG_ESS | VR_FLAG_ERT | VR_FLAG_SHADE | VR_FLAG_CONIC))
         throw Error(VR_EINVAL, "vr_params: unknown flags");
@@ -1789,7 +1793,8 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
                                    c->cdist_p, gtab, gtab_out, c->count_ptr));
         if (gtab_out) c->axtab[c->stream].key = std::move(pub_key);   // valid for later launches on this stream
     } else {
-        const bool dvr = p->mode == VR_MODE_DVR, mip = p->mode == VR_MODE_MIP, iso = p->mode == VR_MODE_ISO;
+        const bool sdvr = p->mode == VR_MODE_SDVR;   // (DVR's state and frame, its own march)
+        const bool dvr = p->mode == VR_MODE_DVR || sdvr, mip = p->mode == VR_MODE_MIP, iso = p->mode == VR_MODE_ISO;
         if (dvr) ensure_dvr(c);
         else if (mip || iso) ensure_mip(c);   // (ISO reads MIP's bounds: a context that renders both builds them once)
         else if (!c->cls_test_valid) classify(c, true);
@@ -1821,6 +1826,13 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             const bool ess = (f.flags & VR_FLAG_ESS) && f.zero_transparent;
             if (dvr_lds_bytes(f, g, ess) > (size_t)kDvrLdsMax) f.sep_tab = 0;
             if (dvr_lds_bytes(f, g, ess) > (size_t)kDvrLdsMax) f.occ_lds = 0;
+            if (sdvr) {   // the Phong coefficients by value per frame, like ISO's
+                SdvrFrame h;
+                h.ka = p->shade_ambient; h.kd = p->shade_diffuse; h.ks = p->shade_specular; h.shininess = p->shade_shininess;
+                hip_check(launch_sdvr_march(f, g, h, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8,
+                                            c->dvr_start.as<float>(), c->dvr_seg.as<float4>(),
+                                            c->dvr_occ.as<uint32_t>(), out, c->stream));
+            } else
             hip_check(launch_dvr_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8, c->dvr_start.as<float>(),
                                        c->dvr_seg.as<float4>(), c->dvr_occ.as<uint32_t>(), out, c->stream));
         } else if (mip) {
@@ -2643,7 +2655,7 @@ int vr_assemble_tiles(vr_ctx* c, int32_t W, int32_t H, int32_t tile_w, int32_t t
 
 int vr_count_samples(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64_t* n_in) {
     if (!c || !cam || !n_in) return VR_EINVAL;
-    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO))
+    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO || p->mode == VR_MODE_SDVR))
         return VR_EINVAL;   // (the counting passes cover VRC and TEST)
     return guard([&] {
         check_params(p);
@@ -2668,8 +2680,8 @@ int vr_count_samples(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64
 // axis_columns_plan's scope), and the tests that pin these counts pin that definition.
 int vr_count_work(vr_ctx* c, const vr_params* p, const vr_camera* cam, vr_work_count* out) {
     if (!c || !cam || !out) return VR_EINVAL;
-    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO))
-        return VR_EINVAL;   // (no counting instantiation of the DVR, MIP and ISO marches)
+    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO || p->mode == VR_MODE_SDVR))
+        return VR_EINVAL;   // (no counting instantiation of the DVR, SDVR, MIP and ISO marches)
     return guard([&] {
         check_params(p);
         set_device(c);

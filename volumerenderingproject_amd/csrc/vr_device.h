@@ -202,6 +202,12 @@ struct IsoFrame {
     int32_t bound_bytes;        // bytes of the cells' upper bounds (one float per cell)
 };
 
+// The SDVR march (vr_sdvr.hip) takes DVR's TestFrame and DvrFrame unchanged and adds the Phong
+// coefficients, by value per launch like IsoFrame's:
+struct SdvrFrame {
+    float ka, kd, ks, shininess;   // vr_params.shade_*
+};
+
 // TransferFunction::getMaterial (TransferFunction.cu:46-55): last closed interval containing v, else 0
 __device__ __forceinline__ int tf_class(const float* lo, const float* hi, int n, float v) {
     int r = 0;

@@ -1,0 +1,400 @@
+// vr_sdvr.hip -- VR_MODE_SDVR for gfx950: VR_MODE_DVR's march with every non-transparent in-volume sample
+// lit by the gradient of the trilinear field at the sample's own position (ISO's six taps, the headlight
+// Phong law of VR_FLAG_SHADE, two-sided).  Its own translation unit so it compiles in parallel with the
+// other marches and leaves their device code alone.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "vr_device.h"
+#include "vr_march.h"
+
+#pragma clang fp contract(off)
+
+namespace vr {
+
+// ------------------------------------------------------------------------------------------------
+// SDVR march, one launch per frame: dvr_march_kernel's text (vr_dvr.hip; repeated rather than shared,
+// vr_march.h) -- 16 x 16 rays per workgroup, work list / background workgroups / hull cull, TEST's
+// position chain with its per-frame B table in LDS, its clip and macro-cell jumps, batches of K = 4
+// samples whose positions and gathers are all issued before any is used, the same templates and the
+// same LDS carve-up (dvr_lds_bytes) -- reading DVR's context state and nothing else.
+//
+// Added per ray: the headlight L = -(p(S - 1) - p(0)) / |.|, from the two end points the clip evaluates
+// anyway.  Added per sample, once its class is known: the lanes whose sample is in the volume with
+// alpha != 0 run six more single samples of the field (sdvr_value_at) around the sample's position,
+// turn the central differences into a normal, face it to the light and put the segment's colour through
+// shade_normal before the blend.  The tap loop is rolled (selects, no indexed arrays) so the batch's
+// live gather registers are not multiplied by six, and a wave none of whose lanes shades the sample
+// skips it.  An alpha-0 sample is never shaded: it stays the exact no-op of both blends that the
+// empty-cell skip (ESS) and the blank-batch skip rely on, so the cell bits and their margin are DVR's.
+// ------------------------------------------------------------------------------------------------
+constexpr int kSdvrK = 4;
+
+// One sample of the field at a point inside the volume -- iso_value_at (vr_iso.hip) restated, so that
+// moving it to a shared header cannot touch ISO's or DVR's register allocation: corners (int)p and
+// min((int)p + 1, d - 1), weights p - (int)p, the gathers of the march (U8: four unaligned dwords of the
+// byte copy; else eight float gathers, a non-finite voxel reading as 0; the edge clamp by selects),
+// lerp1 in y, x, z.  Lanes with ok false issue no load and return 0.
+template <bool U8>
+__device__ __forceinline__ float sdvr_value_at(bool ok, float px, float py, float pz, __amdgpu_buffer_rsrc_t vrs,
+                                               int d3, int d23, int xl, int yl, int zl) {
+    const int ix = (int)px, iy = (int)py, iz = (int)pz;
+    const float dx = __builtin_amdgcn_fractf(px), dy = __builtin_amdgcn_fractf(py), dz = __builtin_amdgcn_fractf(pz);
+    const int base = ix * d23 + iy * d3 + iz;
+    const int ox = ix >= xl ? 0 : d23, oy = iy >= yl ? 0 : d3;
+    const bool lastz = iz >= zl;
+    int off[4];
+    off[0] = base;
+    off[1] = base + oy;
+    off[2] = base + ox;
+    off[3] = base + ox + oy;
+    uint32_t raw[U8 ? 4 : 8];
+#pragma unroll
+    for (int i = 0; i < (U8 ? 4 : 8); ++i) raw[i] = 0u;
+    if (ok) {
+        if (U8) {
+#pragma unroll
+            for (int xy = 0; xy < 4; ++xy) raw[xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy], 0, 0);
+        } else {
+            const int zs = lastz ? 0 : 4;
+#pragma unroll
+            for (int xy = 0; xy < 4; ++xy) {
+                raw[2 * xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy] * 4, 0, 0);
+                raw[2 * xy + 1] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy] * 4 + zs, 0, 0);
+            }
+        }
+    }
+    float c[8];   // corner kk = x << 2 | y << 1 | z
+#pragma unroll
+    for (int xy = 0; xy < 4; ++xy) {
+        if (U8) {
+            const uint32_t z0 = raw[xy] & 0xffu, z1 = (raw[xy] >> 8) & 0xffu;
+            c[2 * xy] = (float)z0;
+            c[2 * xy + 1] = (float)(lastz ? z0 : z1);
+        } else {
+#pragma unroll
+            for (int z = 0; z < 2; ++z) {   // a non-finite voxel reads as 0
+                const uint32_t u = raw[2 * xy + z];
+                c[2 * xy + z] = (u & 0x7f800000u) == 0x7f800000u ? 0.0f : __uint_as_float(u);
+            }
+        }
+    }
+    const float y1 = lerp1(c[0], c[2], dy), y2 = lerp1(c[1], c[3], dy);
+    const float y3 = lerp1(c[4], c[6], dy), y4 = lerp1(c[5], c[7], dy);
+    const float z1 = lerp1(y1, y3, dx), z2 = lerp1(y2, y4, dx);
+    return lerp1(z1, z2, dz);
+}
+
+// (No amdgpu_waves_per_eu cap: profiles/sdvr/resource_usage.txt -- every instantiation fits without
+// scratch left to itself.)
+template <bool F2B, bool ESS, bool U8, bool SEG8, bool SEP>
+__global__ __launch_bounds__(256) void sdvr_march_kernel(TestFrame f, DvrFrame g, SdvrFrame h,
+                                                         const WorkTile* __restrict__ work,
+                                                         const void* __restrict__ vol,
+                                                         const float* __restrict__ gstart,
+                                                         const float4* __restrict__ gseg,
+                                                         const uint32_t* __restrict__ gocc,
+                                                         float4* __restrict__ out) {
+    constexpr int K = kSdvrK;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // LDS: the segments' colours | their starts (search only) | the cell bits (ESS) | the B table (SEP)
+    float4* s_seg = reinterpret_cast<float4*>(smem);
+    float* s_start = reinterpret_cast<float*>(smem + (size_t)g.nseg * sizeof(float4));
+    const bool occ_st = ESS && f.occ_lds;
+    const size_t o_occ = (size_t)g.nseg * sizeof(float4) + (SEG8 ? 0 : ((size_t)g.nseg * 4 + 15) / 16 * 16);
+    uint32_t* s_occ = reinterpret_cast<uint32_t*>(smem + o_occ);
+    float4* s_B = reinterpret_cast<float4*>(smem + o_occ + ((occ_st ? (size_t)f.occ_words * 4 : 0) + 15) / 16 * 16);
+    // first round of loads, unconditional (index clamped, value selected), as in dvr_march_kernel
+    float4 sv[3];
+    float stv[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {   // (nseg <= kMaxDvrSeg = 513 <= 3 * kWgThreads)
+        const int i = (int)threadIdx.x + u * kWgThreads;
+        const int ic = i < g.nseg ? i : 0;
+        sv[u] = gseg[ic];
+        stv[u] = SEG8 ? 0.0f : gstart[ic];
+    }
+    asm volatile("" ::"s"(f.out_tiles), "s"(f.bg_first), "s"(f.n_work), "s"(f.n_hull), "s"(f.W), "s"(f.H));
+    uint32_t ov[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = (int)threadIdx.x + u * kWgThreads;
+        const bool io = occ_st && i < f.occ_words;
+        ov[u] = 0u;
+        if (ESS) { const uint32_t w = gocc[io ? i : 0]; ov[u] = io ? w : 0u; }
+    }
+    const int b = (int)blockIdx.x;
+    const WorkTile wt = work[b < f.n_work ? b : 0];
+    if (b >= f.n_work) return;
+    if (test_background(f, work, wt, out)) return;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+        const int i = (int)threadIdx.x + u * kWgThreads;
+        if (i < g.nseg) {
+            s_seg[i] = sv[u];
+            if (!SEG8) s_start[i] = stv[u];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = (int)threadIdx.x + u * kWgThreads;
+        if (occ_st && i < f.occ_words) s_occ[i] = ov[u];
+    }
+    if (occ_st)
+        for (int i = threadIdx.x + 4 * kWgThreads; i < f.occ_words; i += kWgThreads) s_occ[i] = gocc[i];
+    if (SEP && f.sep_tab) test_stage_B(f, s_B, K);
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t ors = uniform_rsrc(gocc, ESS ? f.occ_words * 4 : 0);
+    auto occ_word = [&](int wi) -> uint32_t {
+        if (f.occ_lds) return s_occ[wi];
+        return __builtin_amdgcn_raw_buffer_load_b32(ors, wi * 4, 0, 0);
+    };
+    // the ERT threshold pinned in a VGPR (test_march_kernel)
+    float ert_eps = f.ert_eps;
+    asm volatile("" : "+v"(ert_eps));
+    int x, y;
+    ray_of_thread(wt, x, y);
+    if (x >= f.W || y >= f.H) return;
+
+    // TEST's position chain, clip and linear model (vr_march.h)
+    TestRay ray;
+    test_ray_init<SEP>(f, x, y, ray);
+    auto position = [&](int s, float p[3]) { test_position<SEP>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
+    int s_begin, s_end;
+    float pa[3], dp[3], idp[3];
+    float L[3] = {0.0f, 0.0f, 0.0f};
+    bool lit = false;   // the ray has a light direction
+    {
+        float pb[3];
+        position(0, pa);
+        position(f.S > 1 ? f.S - 1 : 0, pb);
+        test_clip(f, pa, pb, dp, idp, s_begin, s_end);
+        // headlight along the ray, in voxel space (iso_march_kernel's, from the same two end points)
+        const float ex = pb[0] - pa[0], ey = pb[1] - pa[1], ez = pb[2] - pa[2];
+        const float n2 = (ex * ex + ey * ey) + ez * ez;
+        if (n2 > 0.0f) {
+            const float il = 1.0f / sqrtf(n2);
+            L[0] = -ex * il; L[1] = -ey * il; L[2] = -ez * il;
+            lit = true;
+        }
+    }
+
+    const float4 tf0 = s_seg[g.seg0];
+    // (host: the array is addressable with 32-bit byte offsets)
+    const int d3 = (int)f.d3, d23 = (int)(f.d2 * f.d3);
+    const int xl = (int)f.d1 - 1, yl = (int)f.d2 - 1, zl = (int)f.d3 - 1;
+    const __amdgpu_buffer_rsrc_t vrs = uniform_rsrc(vol, g.vol_bytes);
+    float r, gr, bl, T = 1.0f;
+    if (F2B) { r = 0.0f; gr = 0.0f; bl = 0.0f; }
+    else { r = f.bg[0]; gr = f.bg[1]; bl = f.bg[2]; }
+
+    int s = F2B ? s_begin : s_end - 1;
+    bool done = F2B ? (s >= s_end) : (s < s_begin);
+    float pfirst[3];   // ESS: the position of the batch's first sample, from the empty-cell test
+    while (!done) {
+        if (ESS) {
+            float* p = pfirst;
+            position(s, p);
+            // (bitwise, not short-circuit: && chains compile to exec-mask branches)
+            const bool inside = ((int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
+                                 (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
+                                 (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            int cc[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) cc[c] = inside ? ((int)p[c] >> f.tcb) : 0;
+            const int cell = __mul24(__mul24(cc[0], f.tnc[1]) + cc[1], f.tnc[2]) + cc[2];   // (< 2^18 cells)
+            if (inside && !((occ_word(cell >> 5) >> (cell & 31)) & 1u)) {
+                test_cell_jump<F2B>(f, cc, pa, dp, idp, s_begin, s_end, s, done);
+                continue;
+            }
+        }
+        float w[K][3];
+        bool in[K], lastz[K];
+        int off[K][4];
+        bool any_in = false;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int sk = F2B ? s + k : s - k;
+            const bool valid = F2B ? (sk < s_end) : (sk >= s_begin);
+            float p[3];
+            if (ESS && k == 0) {   // (s did not move since the empty-cell test: the same position)
+                p[0] = pfirst[0]; p[1] = pfirst[1]; p[2] = pfirst[2];
+            } else {
+                position(sk, p);
+            }
+            // 0 <= p < fd as unsigned compares of the bits (test_march_kernel)
+            in[k] = ((int)valid & (int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
+                     (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
+                     (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            any_in |= in[k];
+            int i0[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                i0[c] = (int)p[c];
+                // p - (float)(int)p: for an in-volume sample (p >= 0) that is p - floor(p), which
+                // v_fract_f32 returns exactly; outside, unused
+                w[k][c] = __builtin_amdgcn_fractf(p[c]);
+            }
+            // corner rows (x, y) at xy = x << 1 | y; the clamp to edge: no step at the last x / y
+            const int base = i0[0] * d23 + i0[1] * d3 + i0[2];
+            const int ox = i0[0] >= xl ? 0 : d23, oy = i0[1] >= yl ? 0 : d3;
+            off[k][0] = base;
+            off[k][1] = base + oy;
+            off[k][2] = base + ox;
+            off[k][3] = base + ox + oy;
+            lastz[k] = i0[2] >= zl;
+        }
+        // the gathers of the whole batch, exec-masked per sample (lanes outside skip them)
+        uint32_t raw[K][U8 ? 4 : 8];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            if (in[k]) {
+                if (U8) {
+#pragma unroll
+                    for (int xy = 0; xy < 4; ++xy) raw[k][xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy], 0, 0);
+                } else {
+                    const int zs = lastz[k] ? 0 : 4;
+#pragma unroll
+                    for (int xy = 0; xy < 4; ++xy) {
+                        raw[k][2 * xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4, 0, 0);
+                        raw[k][2 * xy + 1] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4 + zs, 0, 0);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < (U8 ? 4 : 8); ++i) raw[k][i] = 0u;
+            }
+        }
+        // a batch with every lane's samples outside the volume composites TF(0) only: with TF(0)
+        // transparent an exact no-op of either blend (f * (1 - 0) + c * 0 = f, T * (1 - 0) = T)
+        const bool blank = f.zero_transparent && !__any(any_in);
+        if (!blank) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                float c[8];   // corner kk = x << 2 | y << 1 | z
+#pragma unroll
+                for (int xy = 0; xy < 4; ++xy) {
+                    if (U8) {
+                        const uint32_t z0 = raw[k][xy] & 0xffu, z1 = (raw[k][xy] >> 8) & 0xffu;
+                        c[2 * xy] = (float)z0;
+                        c[2 * xy + 1] = (float)(lastz[k] ? z0 : z1);
+                    } else {
+#pragma unroll
+                        for (int z = 0; z < 2; ++z) {   // a non-finite voxel reads as 0
+                            const uint32_t u = raw[k][2 * xy + z];
+                            c[2 * xy + z] = (u & 0x7f800000u) == 0x7f800000u ? 0.0f : __uint_as_float(u);
+                        }
+                    }
+                }
+                const float dx = w[k][0], dy = w[k][1], dz = w[k][2];
+                const float y1 = lerp1(c[0], c[2], dy), y2 = lerp1(c[1], c[3], dy);
+                const float y3 = lerp1(c[4], c[6], dy), y4 = lerp1(c[5], c[7], dy);
+                const float z1 = lerp1(y1, y3, dx), z2 = lerp1(y2, y4, dx);
+                const float v = lerp1(z1, z2, dz);
+                int seg = 0;
+                if (SEG8) {
+#pragma unroll
+                    for (int j = 0; j < kDvrSeg8; ++j) seg += (int)(v >= g.start[j]);
+                } else {
+                    // the last start <= v (start[0] = -inf; a NaN stays in segment 0)
+#pragma unroll
+                    for (int step = 512; step >= 1; step >>= 1) {
+                        const int np = seg + step;
+                        const float st = s_start[min(np, g.nseg - 1)];
+                        seg = (np < g.nseg && v >= st) ? np : seg;
+                    }
+                }
+                const float4 cs = s_seg[seg];
+                float4 cf = in[k] ? cs : tf0;
+                const int sk = F2B ? s + k : s - k;
+                // the shaded samples: in the volume (in[k] holds the range test too) with alpha != 0
+                const bool sh = in[k] && cf.w != 0.0f;
+                if (__any(sh)) {
+                    float ps[3];
+                    position(sk, ps);   // (the batch kept the sample's fractions only: the same position again)
+                    // gradient of the trilinear field at p: taps t = 2 a (q+) and 2 a + 1 (q-) of axis a, both
+                    // in the volume for a lane that shades (selects, no indexed arrays: the loop is rolled)
+                    float gx = 0.0f, gy = 0.0f, gz = 0.0f, vplus = 0.0f;
+#pragma unroll 1
+                    for (int t = 0; t < 6; ++t) {
+                        const int a = t >> 1;
+                        const float pc = a == 0 ? ps[0] : (a == 1 ? ps[1] : ps[2]);
+                        const float top = (float)(a == 0 ? xl : (a == 1 ? yl : zl));
+                        const float qp = fminf(pc + 1.0f, top), qm = fmaxf(pc - 1.0f, 0.0f);
+                        const float q = (t & 1) ? qm : qp;
+                        const float tv = sdvr_value_at<U8>(sh, a == 0 ? q : ps[0], a == 1 ? q : ps[1],
+                                                           a == 2 ? q : ps[2], vrs, d3, d23, xl, yl, zl);
+                        if (t & 1) {
+                            const float span = qp - qm;
+                            const float ga = span > 0.0f ? (vplus - tv) / span : 0.0f;
+                            gx = a == 0 ? ga : gx;
+                            gy = a == 1 ? ga : gy;
+                            gz = a == 2 ? ga : gz;
+                        } else {
+                            vplus = tv;
+                        }
+                    }
+                    const float len2 = (gx * gx + gy * gy) + gz * gz;
+                    float4 nv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    if (lit && len2 > 0.0f) {   // (without a light direction: d = 1, spec = 0, as without a normal)
+                        const float inv = 1.0f / sqrtf(len2);
+                        nv = make_float4(-gx * inv, -gy * inv, -gz * inv, 1.0f);
+                        // two-sided: a normal facing away from the light is negated (exact), so the law's own
+                        // dot product is -ndl
+                        const float ndl = (nv.x * L[0] + nv.y * L[1]) + nv.z * L[2];
+                        if (ndl < 0.0f) { nv.x = -nv.x; nv.y = -nv.y; nv.z = -nv.z; }
+                    }
+                    float cr = cf.x, cg = cf.y, cb = cf.z;
+                    shade_normal(nv, L, h.ka, h.kd, h.ks, h.shininess, cr, cg, cb);
+                    cf.x = sh ? cr : cf.x;
+                    cf.y = sh ? cg : cf.y;
+                    cf.z = sh ? cb : cf.z;
+                }
+                const float a = (F2B ? (sk < s_end) : (sk >= s_begin)) ? cf.w : 0.0f;
+                if (F2B) {
+                    const float wt_ = T * a;
+                    r = fmaf(wt_, cf.x, r); gr = fmaf(wt_, cf.y, gr); bl = fmaf(wt_, cf.z, bl);
+                    T = T * (1.0f - a);
+                } else {
+                    r = r * (1 - a) + cf.x * a;
+                    gr = gr * (1 - a) + cf.y * a;
+                    bl = bl * (1 - a) + cf.z * a;
+                }
+            }
+        }
+        if (F2B && T < ert_eps) done = true;
+        s = F2B ? s + K : s - K;
+        if (F2B ? (s >= s_end) : (s < s_begin)) done = true;
+    }
+    if (F2B) { r = r + T * f.bg[0]; gr = gr + T * f.bg[1]; bl = bl + T * f.bg[2]; }
+    store_pixel(out, out_index(f.out_tiles, wt, x, y, f.H, f.tile_w, f.tile_h), f.out_rgb, r, gr, bl);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Launch wrapper (called from vr_api.cpp)
+// ------------------------------------------------------------------------------------------------
+
+size_t dvr_lds_bytes(const TestFrame& f, const DvrFrame& g, bool ess);   // (vr_dvr.hip: the same carve-up)
+
+hipError_t launch_sdvr_march(const TestFrame& f, const DvrFrame& g, const SdvrFrame& h, const WorkTile* work,
+                             int n_blocks, const void* vol, bool u8, const float* start, const float4* seg,
+                             const uint32_t* occ, float4* out, hipStream_t st) {
+    const bool f2b = (f.flags & 2) != 0, ess = (f.flags & 1) != 0 && f.zero_transparent && occ != nullptr;
+    const bool seg8 = g.nseg <= 1 + kDvrSeg8, sep = f.sep != 0;
+    const size_t lds = dvr_lds_bytes(f, g, ess);
+#define VR_S5(F2B_, ESS_, U8_, SEG8_, SEP_)                                                                      \
+    hipLaunchKernelGGL((sdvr_march_kernel<F2B_, ESS_, U8_, SEG8_, SEP_>), dim3(n_blocks), dim3(kWgThreads), lds, \
+                       st, f, g, h, work, vol, start, seg, occ, out)
+#define VR_S4(F2B_, ESS_, U8_, SEG8_) do { if (sep) VR_S5(F2B_, ESS_, U8_, SEG8_, true); else VR_S5(F2B_, ESS_, U8_, SEG8_, false); } while (0)
+#define VR_S3(F2B_, ESS_, U8_) do { if (seg8) VR_S4(F2B_, ESS_, U8_, true); else VR_S4(F2B_, ESS_, U8_, false); } while (0)
+#define VR_S2(F2B_, ESS_) do { if (u8) VR_S3(F2B_, ESS_, true); else VR_S3(F2B_, ESS_, false); } while (0)
+    if (f2b) { if (ess) VR_S2(true, true); else VR_S2(true, false); }
+    else { if (ess) VR_S2(false, true); else VR_S2(false, false); }
+#undef VR_S2
+#undef VR_S3
+#undef VR_S4
+#undef VR_S5
+    return hipGetLastError();
+}
+
+}  // namespace vr

@@ -25,6 +25,7 @@ VR_MODE_DVR = 6       # trilinear sample of the scalar field, then TF classifica
 VR_MODE_MIP = 7       # maximum-intensity projection of the same trilinear field (no TF)
 VR_MODE_ISO = 8       # shaded first-hit isosurface of the same trilinear field (set_isosurface; no TF)
 VR_ISO_REFINE = 6     # its bisection rounds
+VR_MODE_SDVR = 9      # VR_MODE_DVR with every non-transparent in-volume sample lit (shade_*; no VR_FLAG_SHADE)
 VR_FLAG_ESS = 1
 VR_FLAG_ERT = 2
 VR_FLAG_SHADE = 8
@@ -258,6 +259,9 @@ def default_options(**overrides) -> Options:
 
 
 def default_params(width, height, samples_per_ray, mode=VR_MODE_VRC, flags=0, ert_epsilon=1e-5) -> RenderParams:
+    """vr_params_default with the mode (VR_MODE_VRC, _TEST, _DVR, _MIP, _ISO or _SDVR), flags and ERT threshold
+    set.  VR_MODE_ISO and VR_MODE_SDVR always shade: they read shade_ambient / _diffuse / _specular /
+    _shininess without VR_FLAG_SHADE, which only VR_MODE_VRC accepts."""
     p = RenderParams()
     _check(lib().vr_params_default(width, height, samples_per_ray, C.byref(p)), "vr_params_default")
     p.mode, p.flags, p.ert_epsilon = mode, flags, ert_epsilon
