@@ -155,6 +155,42 @@ extern "C" {
                               vr_count_work: VR_EINVAL; vr_axis_columns_plan reports no column path; culling
                               and vr_visible_tiles as for VR_MODE_DVR.  The mode reads VR_MODE_DVR's
                               context state and builds none of its own; vr_set_isosurface plays no part. */
+#define VR_MODE_CDVR 10    /* VR_MODE_DVR under a piecewise-linear RGBA colour map (vr_set_colormap) in place of
+                              the interval transfer function (no reference mode).  All arithmetic is
+                              float32, every operation rounded on its own (no contraction, IEEE division).
+                              1. Samples: VR_MODE_DVR's, operation for operation: the positions p(x, y, s),
+                              the in-volume test 0 <= p_a < d_a and the value v (corners (int)p and
+                              min((int)p + 1, d - 1), weights p - (int)p, a non-finite voxel reads as 0, the
+                              lerp a*(1 - w) + b*w in y, then x, then z).  No division by cal_max anywhere:
+                              the map lives in voxel units.
+                              2. Colour map C(v) over the points x_0 < x_1 < ... < x_{n-1},
+                              1 <= n <= VR_CMAP_MAX_POINTS: j = the number of i with x_i <= v (a NaN: 0).
+                              j == 0 gives rgba_0 and j == n gives rgba_{n-1}.  Otherwise a = rgba_{j-1},
+                              b = rgba_j, u = min((v - x_{j-1}) * inv_{j-1}, 1.0f) with
+                              inv_i = 1.0f / (x_{i+1} - x_i) computed once on the host, and each of the four
+                              channels is a_k*(1 - u) + b_k*u.  So C(x_i) = rgba_i exactly, and a span whose
+                              two alphas are 0 gives alpha exactly 0.
+                              3. A sample outside the volume has colour C(0.0f).  The mode's "zero
+                              transparent" is C(0.0f).a == 0.0f: where VR_MODE_DVR reads TF(0).a == 0 (the
+                              clip, the visible rectangle, the hull cull, vr_visible_tiles, VR_FLAG_ESS),
+                              this mode reads that.
+                              4. Blend: VR_MODE_DVR's two blends: back to front f = f*(1 - a) + c*a; front
+                              to back with VR_FLAG_ERT and the stop at T < ert_epsilon, within the ERT
+                              tolerance.  Frame alpha is 1.
+                              5. VR_FLAG_ESS is exact (bitwise the exact frame): a cell (min, max of the
+                              voxels its samples can read) is skipped iff every piece of the map meeting
+                              [min - m, max + m], m = 2^-20 max(|min|, |max|), is transparent.  The pieces:
+                              the span [x_i, x_{i+1}), transparent when both end alphas are 0.0f; the lower
+                              tail (-inf, x_0) and the upper tail [x_{n-1}, +inf), transparent when their
+                              one end alpha is 0.0f.  A cell whose widened range is not finite is never
+                              skipped.  Without zero transparency the flag is accepted and skips nothing.
+                              6. VR_FLAG_SHADE / VR_FLAG_CONIC are VR_EINVAL.  cal_max must be finite and
+                              > 0 (VR_EINVAL at render); the size limit is VR_MODE_DVR's (VR_ERANGE).
+                              vr_count_samples / vr_count_marched / vr_count_work: VR_EINVAL;
+                              vr_axis_columns_plan reports no column path.  The interval transfer function
+                              and vr_set_isosurface play no part; the colour map plays no part in any other
+                              mode.                                                                      */
+#define VR_CMAP_MAX_POINTS 256
 
 /* ---- render flags -------------------------------------------------------------------------- */
 #define VR_FLAG_ESS 1      /* empty-space skipping (bitwise exact: skips only alpha-0 samples)  */
@@ -413,6 +449,26 @@ int vr_set_transfer_function(vr_ctx* ctx, const vr_tf_interval* tf, int32_t n_tf
  * part; on a one-process-per-GPU group every rank calls it. */
 int vr_set_isosurface(vr_ctx* ctx, float iso_value, const float rgb[3]);
 int vr_get_isosurface(vr_ctx* ctx, float* iso_value, float rgb[3]);
+
+/* VR_MODE_CDVR's colour map: n control points, x in voxel units (like vr_set_isosurface), strictly
+ * ascending.  A context starts with the grey ramp {(0, (0,0,0,0)), ((float)cal_max, (1,1,1,1))}.
+ * VR_EINVAL for a null argument, n outside 1..VR_CMAP_MAX_POINTS, a non-finite x or colour
+ * component, an alpha outside [0, 1], x not strictly ascending, or a span whose
+ * inv_i = 1.0f / (x_{i+1} - x_i) is not finite.  The call changes device tables (the points and the
+ * mode's empty-cell bits), like vr_set_transfer_function and unlike vr_set_isosurface: they are
+ * rebuilt by the next VR_MODE_CDVR frame, after everything queued, and no other mode's state is
+ * touched.  On a one-process multi-GPU context it applies to every part; on a one-process-per-GPU
+ * group every rank calls it.  vr_get_colormap: VR_ERANGE (with *n_out set) when capacity is too
+ * small. */
+typedef struct {
+    float x;
+    float rgba[4];
+} vr_cmap_point;
+int vr_set_colormap(vr_ctx* ctx, const vr_cmap_point* points, int32_t n);
+int vr_get_colormap(vr_ctx* ctx, vr_cmap_point* out, int32_t capacity, int32_t* n_out);
+/* The law itself on the host, no GPU and no context: rgba_out[4 i ..] = C(v[i]) for i < count, bit
+ * for bit what the march classifies with.  The same checks as vr_set_colormap (and count >= 0). */
+int vr_colormap_eval(const vr_cmap_point* points, int32_t n, const float* v, int64_t count, float* rgba_out);
 
 /* deallocateDeviceMemory (kernel.cu:1072-1093). */
 int vr_destroy(vr_ctx* ctx);

@@ -169,6 +169,10 @@ public:
     void set_isosurface(float iso_value, const float (&rgb)[3]) {
         check(vr_set_isosurface(ctx_, iso_value, rgb), "vr_set_isosurface");
     }
+    // VR_MODE_CDVR: the piecewise-linear RGBA colour map, x in voxel units and strictly ascending
+    void set_colormap(const std::vector<vr_cmap_point>& points) {
+        check(vr_set_colormap(ctx_, points.data(), (int32_t)points.size()), "vr_set_colormap");
+    }
     vr_ctx* handle() const { return ctx_; }
 
     static std::vector<vr_tf_interval> intervals(const TransferFunction& tf) {

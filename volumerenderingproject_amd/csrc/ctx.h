@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/vr_api.h"
+#include "host/colormap.h"
 #include "host/scene.h"
 #include "vr_device.h"
 
@@ -228,6 +229,18 @@ struct vr_ctx {
     // mip_bound
     float iso_value = 0.0f;
     float iso_rgb[3] = {1.0f, 1.0f, 1.0f};
+    // VR_MODE_CDVR (vr_cmap.hip): the colour map as the caller gave it and as the law reads it
+    // (host/colormap.h; create: the grey ramp 0 .. cal_max), C(0.0f) and its transparency -- host
+    // state, set by vr_set_colormap -- and, rebuilt by the next CDVR frame after a change
+    // (cmap_valid), the device tables: the points' (x, inv) and colours and the cells' bits over
+    // dvr_minmax (its own bitmask: dvr_occ follows the interval TF)
+    std::vector<vr_cmap_point> cmap_points;
+    vr::Colormap cmap;
+    float cmap_c0[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    bool cmap_zero_transparent = true;
+    bool cmap_valid = false;
+    vr::DevBuf cmap_xi, cmap_col, cmap_occ;
+    vr::CmapFrame cmap_frame{};
     // TEST: a voxel on the volume's faces is not class 0 (test_faces_kernel; 1 until classified)
     vr::DevBuf faces_flag;
     int32_t test_faces_dirty = 1;

@@ -6,6 +6,8 @@
 //   cls_vrc    uint8 class per voxel for VRC      (TF of max(0,v)/(float)(int)cal_max)
 //   cls_test   uint8 class per voxel for TEST     (TF of (float)(v/cal_max)), built on first use
 //   dvr_*      VR_MODE_DVR / VR_MODE_SDVR: byte copy of the volume, cell min/max and bits, TF segments, built on first use
+//   cmap_*     VR_MODE_CDVR: the colour map's (x, inv) and colours and its own cell bits over dvr_minmax, built on first
+//              use and after vr_set_colormap
 //   mip_bound  VR_MODE_MIP / VR_MODE_ISO: the cells' upper bounds (with DVR's byte copy and cell min/max), built on
 //              first use
 //   maps       3 x 2^D int32 leaf -> voxel maps (the octree leaf grid in closed form)
@@ -79,6 +81,11 @@ hipError_t launch_iso_march(const TestFrame&, const IsoFrame&, const WorkTile*, 
                             float4*, hipStream_t);
 hipError_t launch_sdvr_march(const TestFrame&, const DvrFrame&, const SdvrFrame&, const WorkTile*, int, const void*, bool,
                              const float*, const float4*, const uint32_t*, float4*, hipStream_t);
+hipError_t launch_cmap_march(const TestFrame&, const CmapFrame&, const WorkTile*, int, const void*, bool, const float2*,
+                             const float4*, const uint32_t*, float4*, hipStream_t);
+size_t cmap_lds_bytes(const TestFrame&, const CmapFrame&, bool);
+hipError_t launch_cmap_cells(const float2*, int64_t, const float2*, const float4*, int, unsigned long long*, hipStream_t);
+static_assert(kMaxCmap == VR_CMAP_MAX_POINTS, "vr_device.h and vr_api.h disagree on the colour map's size");
 static_assert(kIsoRefine == VR_ISO_REFINE, "vr_device.h and vr_api.h disagree on the refinement rounds");
 hipError_t launch_assemble(int, int, int, int, int, int, const float4*, float4*, int, hipStream_t);
 hipError_t launch_assemble_list(int, int, int, int, const int32_t*, const float4*, float4, float4*, int, hipStream_t,
@@ -116,6 +123,25 @@ std::vector<TransferFunction::Segment> tf_segments(const vr_tf_interval* tf, int
         iv[i].higher_bound = tf[i].hi;
     }
     return TransferFunction(std::move(iv)).segments(cal_max);
+}
+
+// VR_MODE_CDVR's colour map as host state (validated: colormap_build): the law's tables, C(0.0f) and
+// the mode's zero transparency.  The device tables and the cells' bits follow at the next CDVR frame
+// (ensure_cmap); every cached plan that read the old transparency goes.
+void set_cmap(vr_ctx* c, const vr_cmap_point* points, int n) {
+    Colormap m;
+    if (!colormap_build(points, n, &m)) throw Error(VR_EINVAL, "vr_set_colormap: invalid colour map");
+    c->cmap_points.assign(points, points + n);
+    c->cmap = std::move(m);
+    colormap_eval(c->cmap, 0.0f, c->cmap_c0);
+    c->cmap_zero_transparent = c->cmap_c0[3] == 0.0f;
+    c->cmap_valid = false;
+    c->vis_cache.clear();
+}
+
+// "TF(0) is transparent" as a frame of this mode reads it: VR_MODE_CDVR's is C(0.0f).a == 0
+bool mode_zero_transparent(const vr_ctx* c, const vr_params* p) {
+    return p->mode == VR_MODE_CDVR ? c->cmap_zero_transparent : c->zero_transparent;
 }
 
 void set_device(vr_ctx* c) { hip_check(hipSetDevice(c->device)); }
@@ -608,6 +634,11 @@ vr_ctx* create_common(const float* voxels, bool on_device, int64_t d1, int64_t d
     c->cal_max = cal_max;
     c->max_intensity = (int)cal_max;   // kernel.cu:1151 passes double cal_max as int max_intensity
     c->iso_value = (float)(0.5 * cal_max);
+    {   // VR_MODE_CDVR starts with the grey ramp 0 .. cal_max (a cal_max the mode refuses anyway: one point)
+        const vr_cmap_point ramp[2] = {{0.0f, {0.0f, 0.0f, 0.0f, 0.0f}}, {(float)cal_max, {1.0f, 1.0f, 1.0f, 1.0f}}};
+        Colormap m;
+        set_cmap(c.get(), ramp, colormap_build(ramp, 2, &m) ? 2 : 1);
+    }
     set_tf(c.get(), tf, n_tf);
     c->oct.build(d1, d2, d3);
     const int D = (int)c->oct.maximum_depth;
@@ -808,9 +839,9 @@ WorkCache* frame_list(vr_ctx* c, const vr_params* p, const vr_camera* cam, const
 #ifndef VR_TEST_AXIS_COLUMN_DEAL
 #define VR_TEST_AXIS_COLUMN_DEAL 0
 #endif
-    // (DVR, SDVR, MIP and ISO frames: one general march for every view, its volume read like the corner volume)
+    // (DVR, SDVR, CDVR, MIP and ISO frames: one general march for every view, its volume read like the corner volume)
     const int deal = (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO ||
-                      p->mode == VR_MODE_SDVR ||
+                      p->mode == VR_MODE_SDVR || p->mode == VR_MODE_CDVR ||
                       (p->mode == VR_MODE_TEST && (VR_TEST_AXIS_COLUMN_DEAL || make_test(c, p, cam).axt < 0))) ? 1 : 0;
     std::vector<uint32_t> key = {(uint32_t)W, (uint32_t)H, (uint32_t)tx0, (uint32_t)tx1, (uint32_t)ty0, (uint32_t)ty1,
                                  (uint32_t)ma, (uint32_t)deal};
@@ -866,9 +897,9 @@ int hull_edges(const vr_ctx* c, const vr_params* p, const vr_camera* cam, float 
 // nothing can be visible, 2 when no claim can be made (TEST mode, opaque TF(0), a corner behind a
 // conic camera, a NaN camera), 1 with the points in xy.
 int project_box(const vr_ctx* c, const vr_params* p, const vr_camera* cam, double xy[8][2]) {
-    // (DVR, SDVR, MIP, ISO: TEST's positions and in-volume test)
+    // (DVR, SDVR, CDVR, MIP, ISO: TEST's positions and in-volume test)
     if (p->mode == VR_MODE_TEST || p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO ||
-        p->mode == VR_MODE_SDVR)
+        p->mode == VR_MODE_SDVR || p->mode == VR_MODE_CDVR)
         return project_box_test(c, p, cam, xy);
     if (p->mode != VR_MODE_VRC || !c->zero_transparent) return 2;
     double lo[3], hi[3];
@@ -912,7 +943,8 @@ int project_box(const vr_ctx* c, const vr_params* p, const vr_camera* cam, doubl
 // precision; the float matrices' rounding is far inside the 2-pixel margin visible_rect adds).
 // MIP and ISO frames: a ray without an in-volume sample is the background by definition, whatever TF(0) is.
 int project_box_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam, double xy[8][2]) {
-    if (!c->zero_transparent && p->mode != VR_MODE_MIP && p->mode != VR_MODE_ISO) return 2;
+    // (CDVR: a sample outside the volume is C(0.0f), the colour map's own zero transparency)
+    if (!mode_zero_transparent(c, p) && p->mode != VR_MODE_MIP && p->mode != VR_MODE_ISO) return 2;
     CameraState cs;
     cs.pos = {cam->pos[0], cam->pos[1], cam->pos[2]};
     cs.up = {cam->up[0], cam->up[1], cam->up[2]};
@@ -1165,7 +1197,7 @@ void check_params(const vr_params* p) {
     if (!p || p->width <= 0 || p->height <= 0 || p->samples_per_ray <= 0 || p->width > 65535 || p->height > 65535)
         throw Error(VR_EINVAL, "vr_params: bad width/height/samples_per_ray");
     if (p->mode != VR_MODE_VRC && p->mode != VR_MODE_TEST && p->mode != VR_MODE_DVR && p->mode != VR_MODE_MIP &&
-        p->mode != VR_MODE_ISO && p->mode != VR_MODE_SDVR)
+        p->mode != VR_MODE_ISO && p->mode != VR_MODE_SDVR && p->mode != VR_MODE_CDVR)
         throw Error(VR_EINVAL, "vr_params: unknown mode");
     if (p->flags & ~(VR_FLAG_ESS | VR_FLAG_ERT | VR_FLAG_SHADE | VR_FLAG_CONIC))
         throw Error(VR_EINVAL, "vr_params: unknown flags");
@@ -1337,7 +1369,8 @@ TestFrame make_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam) {
     f.total = c->d[0] * c->d[1] * c->d[2];
     f.fd1 = (float)c->d[0]; f.fd2 = (float)c->d[1]; f.fd3 = (float)c->d[2];
     // (MIP, ISO: samples outside the volume take no part, so the clip and the culls hold for any TF)
-    f.zero_transparent = (c->zero_transparent || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO) ? 1 : 0;
+    // (CDVR: the colour map's C(0.0f).a == 0 in the interval TF's place)
+    f.zero_transparent = (mode_zero_transparent(c, p) || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO) ? 1 : 0;
     f.cls0 = c->cls0_test;
     f.idx64 = (f.total + f.d2 * f.d3 + f.d3 + 1) >= ((int64_t)1 << 31) ? 1 : 0;
     f.tcb = c->tcb;
@@ -1581,6 +1614,7 @@ void ensure_dvr_volume(vr_ctx* c) {
         group_mark(c);
         c->dvr_cells_valid = true;
         c->dvr_tf_valid = false;
+        c->cmap_valid = false;
     }
 }
 
@@ -1620,6 +1654,42 @@ void ensure_dvr(vr_ctx* c) {
         c->dvr_frame = g;
         c->dvr_tf_valid = true;
     }
+}
+
+// VR_MODE_CDVR's lazy state: ensure_dvr_volume and -- whenever the colour map changed -- its device
+// tables (the points' (x, inv) and colours, from the host table the law is evaluated with) and its
+// own cell bits over dvr_minmax.  Nothing here follows the interval TF, and nothing of DVR's follows
+// the colour map: a context that alternates the two modes rebuilds neither.
+void ensure_cmap(vr_ctx* c) {
+    ensure_dvr_volume(c);
+    if (c->cmap_valid) return;
+    const Colormap& m = c->cmap;
+    std::vector<float2> xi((size_t)m.n);
+    std::vector<float4> col((size_t)m.n);
+    CmapFrame g;
+    std::memset(&g, 0, sizeof g);
+    g.n = m.n;
+    for (int k = 0; k < 4; ++k) g.c0[k] = c->cmap_c0[k];
+    for (int i = 0; i < kCmapSmall; ++i) g.x[i] = std::numeric_limits<float>::quiet_NaN();
+    for (int i = 0; i < m.n; ++i) {
+        xi[(size_t)i] = make_float2(m.x[(size_t)i], m.inv[(size_t)i]);
+        col[(size_t)i] = make_float4(m.rgba[(size_t)i * 4], m.rgba[(size_t)i * 4 + 1], m.rgba[(size_t)i * 4 + 2],
+                                     m.rgba[(size_t)i * 4 + 3]);
+        if (m.n <= kCmapSmall) g.x[i] = m.x[(size_t)i];
+    }
+    ctx_sync(c, c->stream);   // (queued launches read the old tables)
+    const int64_t cells = (int64_t)c->dvr_tnc[0] * c->dvr_tnc[1] * c->dvr_tnc[2];
+    c->cmap_xi.ensure((size_t)kMaxCmap * sizeof(float2));
+    c->cmap_col.ensure((size_t)kMaxCmap * sizeof(float4));
+    c->cmap_occ.ensure((size_t)((cells + 63) / 64) * 8);
+    hip_check(hipMemcpyAsync(c->cmap_xi.p, xi.data(), xi.size() * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+    hip_check(hipMemcpyAsync(c->cmap_col.p, col.data(), col.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    hip_check(launch_cmap_cells(c->dvr_minmax.as<float2>(), cells, c->cmap_xi.as<float2>(), c->cmap_col.as<float4>(), m.n,
+                                c->cmap_occ.as<unsigned long long>(), c->stream));
+    group_mark(c);
+    ctx_sync(c, c->stream);   // (xi and col are host temporaries)
+    c->cmap_frame = g;
+    c->cmap_valid = true;
 }
 
 // VR_MODE_MIP's and VR_MODE_ISO's lazy state: ensure_dvr_volume and, on the first frame of either, the cells' upper bounds
@@ -1795,7 +1865,9 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
     } else {
         const bool sdvr = p->mode == VR_MODE_SDVR;   // (DVR's state and frame, its own march)
         const bool dvr = p->mode == VR_MODE_DVR || sdvr, mip = p->mode == VR_MODE_MIP, iso = p->mode == VR_MODE_ISO;
+        const bool cdvr = p->mode == VR_MODE_CDVR;
         if (dvr) ensure_dvr(c);
+        else if (cdvr) ensure_cmap(c);
         else if (mip || iso) ensure_mip(c);   // (ISO reads MIP's bounds: a context that renders both builds them once)
         else if (!c->cls_test_valid) classify(c, true);
         TestFrame f = make_test(c, p, cam);
@@ -1835,6 +1907,24 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             } else
             hip_check(launch_dvr_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8, c->dvr_start.as<float>(),
                                        c->dvr_seg.as<float4>(), c->dvr_occ.as<uint32_t>(), out, c->stream));
+        } else if (cdvr) {
+            // the CDVR march: TEST's frame with DVR's cells under the colour map's own bits, plus the
+            // map's tables (ensure_cmap)
+            const int64_t n = c->d[0] * c->d[1] * c->d[2];
+            const bool u8 = c->dvr_u8_state == 1;
+            f.axt = -1;
+            f.tcb = c->dvr_tcb;
+            for (int a = 0; a < 3; ++a) f.tnc[a] = c->dvr_tnc[a];
+            f.occ_words = (int)(((int64_t)f.tnc[0] * f.tnc[1] * f.tnc[2] + 31) / 32);
+            f.occ_lds = (f.occ_words <= 8192 && c->occ_lds) ? 1 : 0;
+            CmapFrame g = c->cmap_frame;
+            g.vol_bytes = (int32_t)(u8 ? n + 16 : n * 4);   // (the byte copy: a dword at the last voxel stays inside)
+            // LDS budget, DVR's: the B table first, then the cell bits
+            const bool ess = (f.flags & VR_FLAG_ESS) && f.zero_transparent;
+            if (cmap_lds_bytes(f, g, ess) > (size_t)kDvrLdsMax) f.sep_tab = 0;
+            if (cmap_lds_bytes(f, g, ess) > (size_t)kDvrLdsMax) f.occ_lds = 0;
+            hip_check(launch_cmap_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8, c->cmap_xi.as<float2>(),
+                                        c->cmap_col.as<float4>(), c->cmap_occ.as<uint32_t>(), out, c->stream));
         } else if (mip) {
             // the MIP march: TEST's frame with DVR's cells, plus the cells' bounds (ensure_mip)
             const int64_t n = c->d[0] * c->d[1] * c->d[2];
@@ -2017,7 +2107,8 @@ void destroy_ctx_single(vr_ctx* c) {
     for (DevBuf* b : {&c->vol, &c->cls_vrc, &c->cls8, &c->cls_gen, &c->layout_gen, &c->pmaps_gen, &c->pmaps_pad, &c->pmaps_gen_pad, &c->cls_test, &c->maps, &c->pmaps, &c->pmapx64, &c->occ, &c->tf_rgba,
                       &c->tf_lohi, &c->alpha_nz, &c->frame, &c->counter, &c->layout, &c->egress, &c->occ_test,
                       &c->occ_cols, &c->occ_leafcols, &c->cdist, &c->nrm, &c->tcol, &c->tcc, &c->tcc_lay, &c->faces_flag,
-                      &c->dvr_u8, &c->dvr_minmax, &c->dvr_occ, &c->dvr_start, &c->dvr_seg, &c->mip_bound})
+                      &c->dvr_u8, &c->dvr_minmax, &c->dvr_occ, &c->dvr_start, &c->dvr_seg, &c->mip_bound,
+                      &c->cmap_xi, &c->cmap_col, &c->cmap_occ})
         b->reset();
     c->work_cache.clear();
     c->slot_maps.clear();
@@ -2221,6 +2312,30 @@ int vr_get_isosurface(vr_ctx* c, float* iso_value, float rgb[3]) {
     if (!c || !iso_value || !rgb) return VR_EINVAL;
     *iso_value = c->iso_value;
     for (int a = 0; a < 3; ++a) rgb[a] = c->iso_rgb[a];
+    return VR_OK;
+}
+
+// VR_MODE_CDVR's colour map: host state now, the device tables and the cells' bits at the next CDVR
+// frame (ensure_cmap: after everything queued), like vr_set_transfer_function's for DVR.
+int vr_set_colormap(vr_ctx* c, const vr_cmap_point* points, int32_t n) {
+    if (!c || !points) return VR_EINVAL;
+    return guard([&] {
+        Colormap m;
+        if (!colormap_build(points, n, &m)) throw Error(VR_EINVAL, "vr_set_colormap: invalid colour map");
+        struct A { const vr_cmap_point* points; int n; } a{points, (int)n};
+        group_for_each(c, [](vr_ctx* pc, void* p) {
+            const A* x = static_cast<const A*>(p);
+            set_cmap(pc, x->points, x->n);
+        }, &a);
+        return VR_OK;
+    });
+}
+
+int vr_get_colormap(vr_ctx* c, vr_cmap_point* out, int32_t capacity, int32_t* n_out) {
+    if (!c || !out || !n_out || capacity < 0) return VR_EINVAL;
+    *n_out = (int32_t)c->cmap_points.size();
+    if ((size_t)capacity < c->cmap_points.size()) return VR_ERANGE;
+    std::copy(c->cmap_points.begin(), c->cmap_points.end(), out);
     return VR_OK;
 }
 
@@ -2655,7 +2770,8 @@ int vr_assemble_tiles(vr_ctx* c, int32_t W, int32_t H, int32_t tile_w, int32_t t
 
 int vr_count_samples(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64_t* n_in) {
     if (!c || !cam || !n_in) return VR_EINVAL;
-    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO || p->mode == VR_MODE_SDVR))
+    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO || p->mode == VR_MODE_SDVR ||
+              p->mode == VR_MODE_CDVR))
         return VR_EINVAL;   // (the counting passes cover VRC and TEST)
     return guard([&] {
         check_params(p);
@@ -2680,8 +2796,9 @@ int vr_count_samples(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64
 // axis_columns_plan's scope), and the tests that pin these counts pin that definition.
 int vr_count_work(vr_ctx* c, const vr_params* p, const vr_camera* cam, vr_work_count* out) {
     if (!c || !cam || !out) return VR_EINVAL;
-    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO || p->mode == VR_MODE_SDVR))
-        return VR_EINVAL;   // (no counting instantiation of the DVR, SDVR, MIP and ISO marches)
+    if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO || p->mode == VR_MODE_SDVR ||
+              p->mode == VR_MODE_CDVR))
+        return VR_EINVAL;   // (no counting instantiation of the DVR, SDVR, CDVR, MIP and ISO marches)
     return guard([&] {
         check_params(p);
         set_device(c);
@@ -2977,7 +3094,8 @@ int vr_get_volume_info(vr_ctx* c, vr_volume_info* out) {
     uint64_t b = 0;
     for (DevBuf* d : {&c->vol, &c->cls_vrc, &c->cls8, &c->cls_gen, &c->layout_gen, &c->pmaps_gen, &c->pmaps_pad, &c->pmaps_gen_pad, &c->cls_test, &c->maps, &c->pmaps, &c->pmapx64, &c->occ, &c->tf_rgba,
                       &c->tf_lohi, &c->alpha_nz, &c->frame, &c->counter, &c->layout, &c->egress, &c->occ_test, &c->occ_cols, &c->occ_leafcols, &c->cdist, &c->nrm, &c->tcol, &c->tcc, &c->tcc_lay,
-                      &c->dvr_u8, &c->dvr_minmax, &c->dvr_occ, &c->dvr_start, &c->dvr_seg, &c->mip_bound})
+                      &c->dvr_u8, &c->dvr_minmax, &c->dvr_occ, &c->dvr_start, &c->dvr_seg, &c->mip_bound,
+                      &c->cmap_xi, &c->cmap_col, &c->cmap_occ})
         b += d->bytes;
     out->device_bytes = b;
     out->idx64 = c->idx64 ? 1 : 0;

@@ -1,0 +1,345 @@
+// vr_cmap.hip -- VR_MODE_CDVR for gfx950: VR_MODE_DVR's trilinear sample of the scalar field
+// classified by a piecewise-linear RGBA colour map (include/vr_api.h, host/colormap.h) instead of
+// the interval transfer function, and the empty-cell bits that follow that map.  Its own translation
+// unit: the sample block of dvr_march_kernel is restated here (as vr_mip.hip, vr_iso.hip and
+// vr_sdvr.hip do), so vr_dvr.hip's device code stays what it is.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "vr_device.h"
+#include "vr_march.h"
+
+#pragma clang fp contract(off)
+
+namespace vr {
+
+// ------------------------------------------------------------------------------------------------
+// CDVR march, one launch per frame, the shape of dvr_march_kernel: 16 x 16 rays per workgroup, work
+// list / background workgroups / hull cull (test_background), TEST's position chain with its
+// per-frame B table in LDS, its linear-model clip and its macro-cell jumps, batches of K = 4 samples
+// whose positions and gathers are all issued before any is used; the byte path (four unaligned
+// dword gathers) and the float path (eight gathers, a non-finite voxel reads as 0).
+//
+// Per sample, after the value v: j = the number of points x_i <= v; the two colours a = rgba[ja],
+// b = rgba[jb] with ja = max(j - 1, 0), jb = min(j, n - 1), and (x, inv) of point ja, all from the
+// per-workgroup LDS tables; u = min((v - x) * inv, 1) and the four unfused lerps a (1 - u) + b u.
+// Below the first point and from the last one on ja == jb, and the colour is a itself: a select on
+// the lerps' results, no branch (the u of such a sample is never used).
+//
+// SMALL: at most kCmapSmall points: the x are wave-uniform kernel arguments (SGPRs) and j is the sum
+// of kCmapSmall compares (unused x are NaN: never <= v).  Otherwise a branch-free binary search
+// over the x staged in LDS (kMaxCmap = 256 = 2^8: 9 steps).
+//
+// ESS: cells of 2^tcb voxels per axis whose bit in gocc is clear hold no sample with alpha != 0
+// (cmap_cells_kernel); skipping them leaves either blend unchanged bit for bit.
+// ------------------------------------------------------------------------------------------------
+constexpr int kCmapK = 4;
+
+template <bool F2B, bool ESS, bool U8, bool SMALL, bool SEP>
+__global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame g, const WorkTile* __restrict__ work,
+                                                         const void* __restrict__ vol,
+                                                         const float2* __restrict__ gxi,
+                                                         const float4* __restrict__ gcol,
+                                                         const uint32_t* __restrict__ gocc,
+                                                         float4* __restrict__ out) {
+    constexpr int K = kCmapK;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // LDS: the points' colours | their (x, inv) | the cell bits (ESS) | the B table (SEP)
+    float4* s_col = reinterpret_cast<float4*>(smem);
+    float2* s_xi = reinterpret_cast<float2*>(smem + (size_t)g.n * sizeof(float4));
+    const bool occ_st = ESS && f.occ_lds;
+    const size_t o_occ = (size_t)g.n * sizeof(float4) + ((size_t)g.n * sizeof(float2) + 15) / 16 * 16;
+    uint32_t* s_occ = reinterpret_cast<uint32_t*>(smem + o_occ);
+    float4* s_B = reinterpret_cast<float4*>(smem + o_occ + ((occ_st ? (size_t)f.occ_words * 4 : 0) + 15) / 16 * 16);
+    // first round of loads, unconditional (index clamped, value selected): one point (n <= kMaxCmap =
+    // kWgThreads) and 4 cell words per lane and the work tile; a culled work tile (or a
+    // background-only workgroup) stores the background and leaves before any staging
+    const int ip = (int)threadIdx.x < g.n ? (int)threadIdx.x : 0;
+    const float4 cv = gcol[ip];
+    const float2 xv = gxi[ip];
+    asm volatile("" ::"s"(f.out_tiles), "s"(f.bg_first), "s"(f.n_work), "s"(f.n_hull), "s"(f.W), "s"(f.H));
+    uint32_t ov[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = (int)threadIdx.x + u * kWgThreads;
+        const bool io = occ_st && i < f.occ_words;
+        ov[u] = 0u;
+        if (ESS) { const uint32_t w = gocc[io ? i : 0]; ov[u] = io ? w : 0u; }
+    }
+    const int b = (int)blockIdx.x;
+    const WorkTile wt = work[b < f.n_work ? b : 0];
+    if (b >= f.n_work) return;
+    if (test_background(f, work, wt, out)) return;
+    if ((int)threadIdx.x < g.n) {
+        s_col[threadIdx.x] = cv;
+        s_xi[threadIdx.x] = xv;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = (int)threadIdx.x + u * kWgThreads;
+        if (occ_st && i < f.occ_words) s_occ[i] = ov[u];
+    }
+    if (occ_st)
+        for (int i = threadIdx.x + 4 * kWgThreads; i < f.occ_words; i += kWgThreads) s_occ[i] = gocc[i];
+    if (SEP && f.sep_tab) test_stage_B(f, s_B, K);
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t ors = uniform_rsrc(gocc, ESS ? f.occ_words * 4 : 0);
+    auto occ_word = [&](int wi) -> uint32_t {
+        if (f.occ_lds) return s_occ[wi];
+        return __builtin_amdgcn_raw_buffer_load_b32(ors, wi * 4, 0, 0);
+    };
+    // the ERT threshold pinned in a VGPR (test_march_kernel)
+    float ert_eps = f.ert_eps;
+    asm volatile("" : "+v"(ert_eps));
+    int x, y;
+    ray_of_thread(wt, x, y);
+    if (x >= f.W || y >= f.H) return;
+
+    // TEST's position chain, clip and linear model (vr_march.h)
+    TestRay ray;
+    test_ray_init<SEP>(f, x, y, ray);
+    auto position = [&](int s, float p[3]) { test_position<SEP>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
+    int s_begin, s_end;
+    float pa[3], dp[3], idp[3];
+    {
+        float pb[3];
+        position(0, pa);
+        position(f.S > 1 ? f.S - 1 : 0, pb);
+        test_clip(f, pa, pb, dp, idp, s_begin, s_end);
+    }
+
+    const float4 c0 = make_float4(g.c0[0], g.c0[1], g.c0[2], g.c0[3]);
+    const int nl = g.n - 1;
+    // (host: the array is addressable with 32-bit byte offsets)
+    const int d3 = (int)f.d3, d23 = (int)(f.d2 * f.d3);
+    const int xl = (int)f.d1 - 1, yl = (int)f.d2 - 1, zl = (int)f.d3 - 1;
+    const __amdgpu_buffer_rsrc_t vrs = uniform_rsrc(vol, g.vol_bytes);
+    float r, gr, bl, T = 1.0f;
+    if (F2B) { r = 0.0f; gr = 0.0f; bl = 0.0f; }
+    else { r = f.bg[0]; gr = f.bg[1]; bl = f.bg[2]; }
+
+    int s = F2B ? s_begin : s_end - 1;
+    bool done = F2B ? (s >= s_end) : (s < s_begin);
+    float pfirst[3];   // ESS: the position of the batch's first sample, from the empty-cell test
+    while (!done) {
+        if (ESS) {
+            float* p = pfirst;
+            position(s, p);
+            // (bitwise, not short-circuit: && chains compile to exec-mask branches)
+            const bool inside = ((int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
+                                 (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
+                                 (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            int cc[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) cc[c] = inside ? ((int)p[c] >> f.tcb) : 0;
+            const int cell = __mul24(__mul24(cc[0], f.tnc[1]) + cc[1], f.tnc[2]) + cc[2];   // (< 2^18 cells)
+            if (inside && !((occ_word(cell >> 5) >> (cell & 31)) & 1u)) {
+                test_cell_jump<F2B>(f, cc, pa, dp, idp, s_begin, s_end, s, done);
+                continue;
+            }
+        }
+        float w[K][3];
+        bool in[K], lastz[K];
+        int off[K][4];
+        bool any_in = false;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int sk = F2B ? s + k : s - k;
+            const bool valid = F2B ? (sk < s_end) : (sk >= s_begin);
+            float p[3];
+            if (ESS && k == 0) {   // (s did not move since the empty-cell test: the same position)
+                p[0] = pfirst[0]; p[1] = pfirst[1]; p[2] = pfirst[2];
+            } else {
+                position(sk, p);
+            }
+            // 0 <= p < fd as unsigned compares of the bits (test_march_kernel)
+            in[k] = ((int)valid & (int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
+                     (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
+                     (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            any_in |= in[k];
+            int i0[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                i0[c] = (int)p[c];
+                // p - (float)(int)p: for an in-volume sample (p >= 0) that is p - floor(p), which
+                // v_fract_f32 returns exactly; outside, unused
+                w[k][c] = __builtin_amdgcn_fractf(p[c]);
+            }
+            // corner rows (x, y) at xy = x << 1 | y; the clamp to edge: no step at the last x / y
+            const int base = i0[0] * d23 + i0[1] * d3 + i0[2];
+            const int ox = i0[0] >= xl ? 0 : d23, oy = i0[1] >= yl ? 0 : d3;
+            off[k][0] = base;
+            off[k][1] = base + oy;
+            off[k][2] = base + ox;
+            off[k][3] = base + ox + oy;
+            lastz[k] = i0[2] >= zl;
+        }
+        // the gathers of the whole batch, exec-masked per sample (lanes outside skip them)
+        uint32_t raw[K][U8 ? 4 : 8];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            if (in[k]) {
+                if (U8) {
+#pragma unroll
+                    for (int xy = 0; xy < 4; ++xy) raw[k][xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy], 0, 0);
+                } else {
+                    const int zs = lastz[k] ? 0 : 4;
+#pragma unroll
+                    for (int xy = 0; xy < 4; ++xy) {
+                        raw[k][2 * xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4, 0, 0);
+                        raw[k][2 * xy + 1] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4 + zs, 0, 0);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < (U8 ? 4 : 8); ++i) raw[k][i] = 0u;
+            }
+        }
+        // a batch with every lane's samples outside the volume composites C(0) only: with C(0)
+        // transparent an exact no-op of either blend (f * (1 - 0) + c * 0 = f, T * (1 - 0) = T)
+        const bool blank = f.zero_transparent && !__any(any_in);
+        if (!blank) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                float c[8];   // corner kk = x << 2 | y << 1 | z
+#pragma unroll
+                for (int xy = 0; xy < 4; ++xy) {
+                    if (U8) {
+                        const uint32_t z0 = raw[k][xy] & 0xffu, z1 = (raw[k][xy] >> 8) & 0xffu;
+                        c[2 * xy] = (float)z0;
+                        c[2 * xy + 1] = (float)(lastz[k] ? z0 : z1);
+                    } else {
+#pragma unroll
+                        for (int z = 0; z < 2; ++z) {   // a non-finite voxel reads as 0
+                            const uint32_t u = raw[k][2 * xy + z];
+                            c[2 * xy + z] = (u & 0x7f800000u) == 0x7f800000u ? 0.0f : __uint_as_float(u);
+                        }
+                    }
+                }
+                const float dx = w[k][0], dy = w[k][1], dz = w[k][2];
+                const float y1 = lerp1(c[0], c[2], dy), y2 = lerp1(c[1], c[3], dy);
+                const float y3 = lerp1(c[4], c[6], dy), y4 = lerp1(c[5], c[7], dy);
+                const float z1 = lerp1(y1, y3, dx), z2 = lerp1(y2, y4, dx);
+                const float v = lerp1(z1, z2, dz);
+                int j = 0;   // the points x_i <= v (a NaN: none)
+                if (SMALL) {
+#pragma unroll
+                    for (int i = 0; i < kCmapSmall; ++i) j += (int)(v >= g.x[i]);
+                } else {
+#pragma unroll
+                    for (int step = kMaxCmap; step >= 1; step >>= 1) {
+                        const int np = j + step;
+                        const float xs = s_xi[min(np, g.n) - 1].x;
+                        j = (np <= g.n && v >= xs) ? np : j;
+                    }
+                }
+                const int ja = max(j - 1, 0), jb = min(j, nl);
+                const float2 xi = s_xi[ja];
+                const float4 ca = s_col[ja], cb = s_col[jb];
+                const float u = fminf((v - xi.x) * xi.y, 1.0f);
+                const float u1 = 1.0f - u;
+                const bool flat = ja == jb;   // below x_0, or from x_{n-1} on: the end colour itself
+                float4 cs;
+                cs.x = flat ? ca.x : ca.x * u1 + cb.x * u;
+                cs.y = flat ? ca.y : ca.y * u1 + cb.y * u;
+                cs.z = flat ? ca.z : ca.z * u1 + cb.z * u;
+                cs.w = flat ? ca.w : ca.w * u1 + cb.w * u;
+                const float4 cf = in[k] ? cs : c0;
+                const int sk = F2B ? s + k : s - k;
+                const float a = (F2B ? (sk < s_end) : (sk >= s_begin)) ? cf.w : 0.0f;
+                if (F2B) {
+                    const float wt_ = T * a;
+                    r = fmaf(wt_, cf.x, r); gr = fmaf(wt_, cf.y, gr); bl = fmaf(wt_, cf.z, bl);
+                    T = T * (1.0f - a);
+                } else {
+                    r = r * (1 - a) + cf.x * a;
+                    gr = gr * (1 - a) + cf.y * a;
+                    bl = bl * (1 - a) + cf.z * a;
+                }
+            }
+        }
+        if (F2B && T < ert_eps) done = true;
+        s = F2B ? s + K : s - K;
+        if (F2B ? (s >= s_end) : (s < s_begin)) done = true;
+    }
+    if (F2B) { r = r + T * f.bg[0]; gr = gr + T * f.bg[1]; bl = bl + T * f.bg[2]; }
+    store_pixel(out, out_index(f.out_tiles, wt, x, y, f.H, f.tile_w, f.tile_h), f.out_rgb, r, gr, bl);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Cell bits of the colour map, over dvr_minmax_kernel's cells (rebuilt on every vr_set_colormap): a
+// cell is empty (bit clear) iff every piece of the map meeting [min - m, max + m] is transparent,
+// m = 2^-20 max(|min|, |max|) (the margin derived at dvr_cells_kernel: the unfused three-level lerp
+// of values in [min, max] ends within 6 ulps of that range).  The pieces: the lower tail
+// (-inf, x_0) with alpha_0, the spans [x_i, x_{i+1}) with both end alphas, the upper tail
+// [x_{n-1}, +inf) with alpha_{n-1}.  A value in a span with both end alphas 0 has alpha
+// 0 (1 - u) + 0 u = 0 exactly, whatever u in [0, 1] is.  A widened range that is not finite keeps
+// the cell.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void cmap_cells_kernel(const float2* __restrict__ mm, int64_t ncells,
+                                                         const float2* __restrict__ xi,
+                                                         const float4* __restrict__ col, int n,
+                                                         unsigned long long* __restrict__ occ) {
+    const int64_t cell = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool occupied = false;
+    if (cell < ncells) {
+        const float2 r = mm[cell];
+        const float m = fmaxf(fabsf(r.x), fabsf(r.y)) * 9.5367431640625e-07f;   // 2^-20
+        const float lo = r.x - m, hi = r.y + m;
+        const bool finite = (__float_as_uint(lo) & 0x7f800000u) != 0x7f800000u &&
+                            (__float_as_uint(hi) & 0x7f800000u) != 0x7f800000u;
+        occupied = !finite;
+        occupied = occupied || (lo < xi[0].x && col[0].w != 0.0f);
+        occupied = occupied || (hi >= xi[n - 1].x && col[n - 1].w != 0.0f);
+        for (int i = 0; i + 1 < n; ++i) {
+            const bool meets = xi[i].x <= hi && xi[i + 1].x > lo;
+            occupied = occupied || (meets && (col[i].w != 0.0f || col[i + 1].w != 0.0f));
+        }
+    }
+    const unsigned long long mask = __ballot(occupied);
+    if ((threadIdx.x & 63) == 0 && cell < ncells) occ[cell >> 6] = mask;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Launch wrappers (called from vr_api.cpp)
+// ------------------------------------------------------------------------------------------------
+
+// LDS bytes of a CDVR workgroup (host: DVR's budget logic -- the B table is dropped, then the cell
+// bits, when the sum would pass kDvrLdsMax)
+size_t cmap_lds_bytes(const TestFrame& f, const CmapFrame& g, bool ess) {
+    return (size_t)g.n * sizeof(float4) + ((size_t)g.n * sizeof(float2) + 15) / 16 * 16 +
+           (((ess && f.occ_lds) ? (size_t)f.occ_words * 4 : 0) + 15) / 16 * 16 +
+           ((f.sep && f.sep_tab) ? (size_t)(f.S + 2 * kCmapK) * sizeof(float4) : 0);
+}
+
+hipError_t launch_cmap_march(const TestFrame& f, const CmapFrame& g, const WorkTile* work, int n_blocks, const void* vol,
+                             bool u8, const float2* xi, const float4* col, const uint32_t* occ, float4* out,
+                             hipStream_t st) {
+    const bool f2b = (f.flags & 2) != 0, ess = (f.flags & 1) != 0 && f.zero_transparent && occ != nullptr;
+    const bool small = g.n <= kCmapSmall, sep = f.sep != 0;
+    const size_t lds = cmap_lds_bytes(f, g, ess);
+#define VR_C5(F2B_, ESS_, U8_, SMALL_, SEP_)                                                                      \
+    hipLaunchKernelGGL((cmap_march_kernel<F2B_, ESS_, U8_, SMALL_, SEP_>), dim3(n_blocks), dim3(kWgThreads), lds, \
+                       st, f, g, work, vol, xi, col, occ, out)
+#define VR_C4(F2B_, ESS_, U8_, SMALL_) do { if (sep) VR_C5(F2B_, ESS_, U8_, SMALL_, true); else VR_C5(F2B_, ESS_, U8_, SMALL_, false); } while (0)
+#define VR_C3(F2B_, ESS_, U8_) do { if (small) VR_C4(F2B_, ESS_, U8_, true); else VR_C4(F2B_, ESS_, U8_, false); } while (0)
+#define VR_C2(F2B_, ESS_) do { if (u8) VR_C3(F2B_, ESS_, true); else VR_C3(F2B_, ESS_, false); } while (0)
+    if (f2b) { if (ess) VR_C2(true, true); else VR_C2(true, false); }
+    else { if (ess) VR_C2(false, true); else VR_C2(false, false); }
+#undef VR_C2
+#undef VR_C3
+#undef VR_C4
+#undef VR_C5
+    return hipGetLastError();
+}
+
+hipError_t launch_cmap_cells(const float2* mm, int64_t ncells, const float2* xi, const float4* col, int n,
+                             unsigned long long* occ, hipStream_t st) {
+    hipLaunchKernelGGL(cmap_cells_kernel, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, st, mm, ncells, xi, col,
+                       n, occ);
+    return hipGetLastError();
+}
+
+}  // namespace vr

@@ -208,6 +208,18 @@ struct SdvrFrame {
     float ka, kd, ks, shininess;   // vr_params.shade_*
 };
 
+// The CDVR march (vr_cmap.hip) takes DVR's TestFrame (zero_transparent = C(0.0f).a == 0, the cells
+// those of its own bitmask) and adds the colour map: n points, their (x, inv) and colours in device
+// tables (host/colormap.h), C(0.0f) by value, and for a small map the x as wave-uniform arguments.
+constexpr int kCmapSmall = 8;                // up to 8 points: the span index is a sum of compares
+constexpr int kMaxCmap = 256;                // VR_CMAP_MAX_POINTS (one point per lane of a workgroup)
+struct CmapFrame {
+    int32_t n;                  // points
+    int32_t vol_bytes;          // bytes of the array the corner gathers read (their buffer bound)
+    float c0[4];                // C(0.0f): a sample outside the volume
+    float x[kCmapSmall];        // n <= kCmapSmall: x[0 .. n), the rest NaN (no value is >= NaN)
+};
+
 // TransferFunction::getMaterial (TransferFunction.cu:46-55): last closed interval containing v, else 0
 __device__ __forceinline__ int tf_class(const float* lo, const float* hi, int n, float v) {
     int r = 0;

@@ -26,6 +26,8 @@ VR_MODE_MIP = 7       # maximum-intensity projection of the same trilinear field
 VR_MODE_ISO = 8       # shaded first-hit isosurface of the same trilinear field (set_isosurface; no TF)
 VR_ISO_REFINE = 6     # its bisection rounds
 VR_MODE_SDVR = 9      # VR_MODE_DVR with every non-transparent in-volume sample lit (shade_*; no VR_FLAG_SHADE)
+VR_MODE_CDVR = 10     # VR_MODE_DVR under a piecewise-linear RGBA colour map (set_colormap; no TF)
+VR_CMAP_MAX_POINTS = 256
 VR_FLAG_ESS = 1
 VR_FLAG_ERT = 2
 VR_FLAG_SHADE = 8
@@ -47,6 +49,7 @@ EXPORTED = [
     "vr_create_multi", "vr_comm_unique_id", "vr_create_rank", "vr_group_info", "vr_group_tiles", "vr_render_png",
     "vr_render_batch", "vr_create_multi_ex", "vr_group_timing_read", "vr_count_work", "vr_group_traffic_read",
     "vr_axis_columns_plan", "vr_tf_segments", "vr_set_isosurface", "vr_get_isosurface",
+    "vr_set_colormap", "vr_get_colormap", "vr_colormap_eval",
 ]
 VR_COMM_ID_BYTES = 128
 VR_TRANSPORT_NONE, VR_TRANSPORT_RCCL, VR_TRANSPORT_PEER_COPY = 0, 1, 2
@@ -82,6 +85,11 @@ class Camera(C.Structure):
 
 class TFInterval(C.Structure):
     _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("rgba", C.c_float * 4)]
+
+
+class CmapPoint(C.Structure):
+    """vr_cmap_point: a control point of VR_MODE_CDVR's colour map, x in voxel units."""
+    _fields_ = [("x", C.c_float), ("rgba", C.c_float * 4)]
 
 
 class RenderParams(C.Structure):
@@ -174,6 +182,9 @@ def lib():
         "vr_set_transfer_function": ([vp, P(TFInterval), C.c_int32], C.c_int),
         "vr_set_isosurface": ([vp, C.c_float, P(C.c_float)], C.c_int),
         "vr_get_isosurface": ([vp, P(C.c_float), P(C.c_float)], C.c_int),
+        "vr_set_colormap": ([vp, P(CmapPoint), C.c_int32], C.c_int),
+        "vr_get_colormap": ([vp, P(CmapPoint), C.c_int32, P(C.c_int32)], C.c_int),
+        "vr_colormap_eval": ([P(CmapPoint), C.c_int32, P(C.c_float), C.c_int64, P(C.c_float)], C.c_int),
         "vr_destroy": ([vp], C.c_int),
         "vr_render": ([vp, P(RenderParams), P(Camera), vp, C.c_int32], C.c_int),
         "vr_render_tiles": ([vp, P(RenderParams), P(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp,
@@ -258,8 +269,29 @@ def default_options(**overrides) -> Options:
     return o
 
 
+def _cmap_array(points):
+    pts = list(points)
+    arr = (CmapPoint * max(1, len(pts)))()
+    for i, (x, rgba) in enumerate(pts):
+        arr[i].x = float(x)
+        for k in range(4):
+            arr[i].rgba[k] = float(rgba[k])
+    return arr if pts else (CmapPoint * 0)()
+
+
+def colormap_eval(points, v) -> np.ndarray:
+    """vr_colormap_eval: VR_MODE_CDVR's colour map C at the float32 values v, on the host (no GPU, no
+    context), bit for bit what the march classifies with.  Returns v.shape + (4,) float32."""
+    arr = _cmap_array(points)
+    vv = np.ascontiguousarray(v, np.float32)
+    out = np.empty(vv.shape + (4,), np.float32)
+    _check(lib().vr_colormap_eval(arr, len(arr), vv.ctypes.data_as(C.POINTER(C.c_float)), vv.size,
+                                  out.ctypes.data_as(C.POINTER(C.c_float))), "vr_colormap_eval")
+    return out
+
+
 def default_params(width, height, samples_per_ray, mode=VR_MODE_VRC, flags=0, ert_epsilon=1e-5) -> RenderParams:
-    """vr_params_default with the mode (VR_MODE_VRC, _TEST, _DVR, _MIP, _ISO or _SDVR), flags and ERT threshold
+    """vr_params_default with the mode (VR_MODE_VRC, _TEST, _DVR, _MIP, _ISO, _SDVR or _CDVR), flags and ERT threshold
     set.  VR_MODE_ISO and VR_MODE_SDVR always shade: they read shade_ambient / _diffuse / _specular /
     _shininess without VR_FLAG_SHADE, which only VR_MODE_VRC accepts."""
     p = RenderParams()
@@ -487,6 +519,19 @@ class VolumeRenderer:
         iso, c = C.c_float(), (C.c_float * 3)()
         _check(lib().vr_get_isosurface(self._ctx, C.byref(iso), c), "vr_get_isosurface")
         return iso.value, (c[0], c[1], c[2])
+
+    def set_colormap(self, points):
+        """VR_MODE_CDVR's colour map: a sequence of (x, (r, g, b, a)), x in voxel units and strictly
+        ascending.  The device tables and the mode's empty-cell bits follow at the next CDVR frame."""
+        arr = _cmap_array(points)
+        _check(lib().vr_set_colormap(self._ctx, arr, len(arr)), "vr_set_colormap")
+
+    @property
+    def colormap(self):
+        """[(x, (r, g, b, a)), ...] as the context holds them (float32)."""
+        arr, n = (CmapPoint * VR_CMAP_MAX_POINTS)(), C.c_int32()
+        _check(lib().vr_get_colormap(self._ctx, arr, VR_CMAP_MAX_POINTS, C.byref(n)), "vr_get_colormap")
+        return [(arr[i].x, tuple(arr[i].rgba)) for i in range(n.value)]
 
     def render(self, params: RenderParams, camera: Camera) -> np.ndarray:
         """Host frame, shape (W, H, 4), x-major like the reference's screen buffer."""
