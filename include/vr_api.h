@@ -191,6 +191,48 @@ extern "C" {
                               and vr_set_isosurface play no part; the colour map plays no part in any other
                               mode.                                                                      */
 #define VR_CMAP_MAX_POINTS 256
+#define VR_MODE_SCDVR 11   /* VR_MODE_CDVR lit as VR_MODE_SDVR lights, with gradient-magnitude opacity: the
+                              colour map's ramps, a lit surface, and flat tissue made transparent (no
+                              reference mode).  All arithmetic is float32, every operation rounded on its
+                              own (no contraction, IEEE division and square root).
+                              1. Samples: VR_MODE_CDVR's, operation for operation: the positions p(x, y, s),
+                              the in-volume test, the value v and the colour (r, g, b, a) = C(v) under the
+                              context's colour map (vr_set_colormap).  A sample outside the volume has the
+                              colour C(0.0f); it is neither lit nor modulated.
+                              2. Lit samples: a sample is lit when it lies in the volume and has a != 0.0f.
+                              Every other sample keeps its CDVR colour and alpha untouched, so an alpha-0
+                              sample stays the exact no-op that CDVR's empty-space skipping relies on.
+                              3. Gradient at the sample's own position: VR_MODE_SDVR's step 3 verbatim (the
+                              six taps q+ = min(p_a + 1, d_a - 1), q- = max(p_a - 1, 0),
+                              g_a = (v+ - v-) / (q+ - q-), 0 when the span is 0;
+                              len2 = (g_x^2 + g_y^2) + g_z^2; N = -g * (1.0f / sqrtf(len2)) when len2 > 0).
+                              In addition mag = sqrtf(len2).
+                              4. Gradient opacity: the alpha of a lit sample becomes a' = a * G(mag), with or
+                              without a normal.  G is the scalar piecewise-linear map over the points
+                              (m_i, w_i) of vr_set_gradient_opacity, m strictly ascending,
+                              1 <= n <= VR_GOPA_MAX_POINTS, evaluated by VR_MODE_CDVR's step 2 with one
+                              channel: j = the number of i with m_i <= mag (a NaN: 0); j == 0 gives w_0 and
+                              j == n gives w_{n-1}; otherwise u = min((mag - m_{j-1}) * inv_{j-1}, 1.0f) with
+                              inv_i = 1.0f / (m_{i+1} - m_i) computed once on the host, and the weight is
+                              w_{j-1}*(1 - u) + w_j*u.  A context starts with the single point (0, 1):
+                              G == 1 and a' = a bit for bit.  A weight of 0 does not skip the sample: it is
+                              lit and blended with a' = 0.
+                              5. Light, two-sided lighting, colour: VR_MODE_SDVR's steps 4 to 6 with
+                              c = C(v)'s r, g, b and vr_params.shade_* read without VR_FLAG_SHADE:
+                              c' = c * (ka + kd*d) + spec.
+                              6. Blend: VR_MODE_DVR's two blends with c' and a'.  Frame alpha is 1.
+                              7. VR_FLAG_ESS is exact (bitwise the exact frame) and reads VR_MODE_CDVR's own
+                              cell bits: a skipped cell holds only samples with a == 0, which step 2 leaves
+                              untouched.  VR_FLAG_ERT as in VR_MODE_CDVR.  "Zero transparent" is
+                              C(0.0f).a == 0.0f, as in VR_MODE_CDVR (the clip, the culls, vr_visible_tiles).
+                              8. VR_FLAG_SHADE / VR_FLAG_CONIC are VR_EINVAL; the cal_max and size limits
+                              are VR_MODE_CDVR's.  vr_count_samples / vr_count_marched / vr_count_work:
+                              VR_EINVAL; vr_axis_columns_plan reports no column path.
+                              9. The mode reads VR_MODE_CDVR's context state and builds no device table of
+                              its own: alternating the two modes rebuilds nothing.  The interval transfer
+                              function and vr_set_isosurface play no part; G plays no part in any other
+                              mode.                                                                      */
+#define VR_GOPA_MAX_POINTS 16
 
 /* ---- render flags -------------------------------------------------------------------------- */
 #define VR_FLAG_ESS 1      /* empty-space skipping (bitwise exact: skips only alpha-0 samples)  */
@@ -469,6 +511,25 @@ int vr_get_colormap(vr_ctx* ctx, vr_cmap_point* out, int32_t capacity, int32_t* 
 /* The law itself on the host, no GPU and no context: rgba_out[4 i ..] = C(v[i]) for i < count, bit
  * for bit what the march classifies with.  The same checks as vr_set_colormap (and count >= 0). */
 int vr_colormap_eval(const vr_cmap_point* points, int32_t n, const float* v, int64_t count, float* rgba_out);
+
+/* VR_MODE_SCDVR's gradient-opacity map G: n control points (m, w), m the gradient magnitude in voxel
+ * units per voxel, strictly ascending; w the factor on the lit sample's alpha.  A context starts with
+ * the single point (0, 1).  VR_EINVAL for a null argument, n outside 1..VR_GOPA_MAX_POINTS, a
+ * non-finite m or w, a w outside [0, 1], m not strictly ascending, or a span whose
+ * inv_i = 1.0f / (m_{i+1} - m_i) is not finite.  Host state only, like vr_set_isosurface: the table
+ * travels to the march by value with each launch, so a call between queued asynchronous frames needs
+ * no synchronisation, rebuilds nothing and changes no cached plan; each frame shows the G current when
+ * it was enqueued.  Multi-GPU semantics are vr_set_isosurface's.  vr_get_gradient_opacity: VR_ERANGE
+ * (with *n_out set) when capacity is too small. */
+typedef struct {
+    float m;
+    float w;
+} vr_gopa_point;
+int vr_set_gradient_opacity(vr_ctx* ctx, const vr_gopa_point* points, int32_t n);
+int vr_get_gradient_opacity(vr_ctx* ctx, vr_gopa_point* out, int32_t capacity, int32_t* n_out);
+/* The law itself on the host, no GPU and no context: w_out[i] = G(mag[i]) for i < count, bit for bit
+ * what the march scales alpha with.  The same checks as vr_set_gradient_opacity (and count >= 0). */
+int vr_gradient_opacity_eval(const vr_gopa_point* points, int32_t n, const float* mag, int64_t count, float* w_out);
 
 /* deallocateDeviceMemory (kernel.cu:1072-1093). */
 int vr_destroy(vr_ctx* ctx);

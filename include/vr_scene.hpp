@@ -173,6 +173,10 @@ public:
     void set_colormap(const std::vector<vr_cmap_point>& points) {
         check(vr_set_colormap(ctx_, points.data(), (int32_t)points.size()), "vr_set_colormap");
     }
+    // VR_MODE_SCDVR: the gradient-opacity map, m strictly ascending and w in [0, 1]
+    void set_gradient_opacity(const std::vector<vr_gopa_point>& points) {
+        check(vr_set_gradient_opacity(ctx_, points.data(), (int32_t)points.size()), "vr_set_gradient_opacity");
+    }
     vr_ctx* handle() const { return ctx_; }
 
     static std::vector<vr_tf_interval> intervals(const TransferFunction& tf) {

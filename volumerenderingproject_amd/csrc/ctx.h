@@ -241,6 +241,11 @@ struct vr_ctx {
     bool cmap_valid = false;
     vr::DevBuf cmap_xi, cmap_col, cmap_occ;
     vr::CmapFrame cmap_frame{};
+    // VR_MODE_SCDVR (vr_scdvr.hip) reads the CDVR state above and adds host state only: the
+    // gradient-opacity map as the caller gave it and as the law reads it (host/colormap.h; create: the
+    // single point (0, 1)), set by vr_set_gradient_opacity and passed to the march by value per launch
+    std::vector<vr_gopa_point> gopa_points;
+    vr::Gopa gopa;
     // TEST: a voxel on the volume's faces is not class 0 (test_faces_kernel; 1 until classified)
     vr::DevBuf faces_flag;
     int32_t test_faces_dirty = 1;

@@ -6,7 +6,7 @@
 //   cls_vrc    uint8 class per voxel for VRC      (TF of max(0,v)/(float)(int)cal_max)
 //   cls_test   uint8 class per voxel for TEST     (TF of (float)(v/cal_max)), built on first use
 //   dvr_*      VR_MODE_DVR / VR_MODE_SDVR: byte copy of the volume, cell min/max and bits, TF segments, built on first use
-//   cmap_*     VR_MODE_CDVR: the colour map's (x, inv) and colours and its own cell bits over dvr_minmax, built on first
+//   cmap_*     VR_MODE_CDVR / VR_MODE_SCDVR: the colour map's (x, inv) and colours and its own cell bits over dvr_minmax, built on first
 //              use and after vr_set_colormap
 //   mip_bound  VR_MODE_MIP / VR_MODE_ISO: the cells' upper bounds (with DVR's byte copy and cell min/max), built on
 //              first use
@@ -85,6 +85,10 @@ hipError_t launch_cmap_march(const TestFrame&, const CmapFrame&, const WorkTile*
                              const float4*, const uint32_t*, float4*, hipStream_t);
 size_t cmap_lds_bytes(const TestFrame&, const CmapFrame&, bool);
 hipError_t launch_cmap_cells(const float2*, int64_t, const float2*, const float4*, int, unsigned long long*, hipStream_t);
+hipError_t launch_scdvr_march(const TestFrame&, const CmapFrame&, const ScdvrFrame&, const WorkTile*, int, const void*, bool,
+                              const float2*, const float4*, const uint32_t*, float4*, hipStream_t);
+size_t scdvr_lds_bytes(const TestFrame&, const CmapFrame&, bool);
+static_assert(kMaxGopa == VR_GOPA_MAX_POINTS, "vr_device.h and vr_api.h disagree on the gradient-opacity map's size");
 static_assert(kMaxCmap == VR_CMAP_MAX_POINTS, "vr_device.h and vr_api.h disagree on the colour map's size");
 static_assert(kIsoRefine == VR_ISO_REFINE, "vr_device.h and vr_api.h disagree on the refinement rounds");
 hipError_t launch_assemble(int, int, int, int, int, int, const float4*, float4*, int, hipStream_t);
@@ -139,9 +143,21 @@ void set_cmap(vr_ctx* c, const vr_cmap_point* points, int n) {
     c->vis_cache.clear();
 }
 
-// "TF(0) is transparent" as a frame of this mode reads it: VR_MODE_CDVR's is C(0.0f).a == 0
+// The modes that classify with the colour map and read its context state: CDVR and its lit variant
+bool mode_cmap(const vr_params* p) { return p->mode == VR_MODE_CDVR || p->mode == VR_MODE_SCDVR; }
+
+// "TF(0) is transparent" as a frame of this mode reads it: VR_MODE_CDVR's and VR_MODE_SCDVR's is C(0.0f).a == 0
 bool mode_zero_transparent(const vr_ctx* c, const vr_params* p) {
-    return p->mode == VR_MODE_CDVR ? c->cmap_zero_transparent : c->zero_transparent;
+    return mode_cmap(p) ? c->cmap_zero_transparent : c->zero_transparent;
+}
+
+// VR_MODE_SCDVR's gradient-opacity map as host state (validated: gopa_build).  Nothing on the device
+// and no cached plan follows it: the march takes it by value per launch.
+void set_gopa(vr_ctx* c, const vr_gopa_point* points, int n) {
+    Gopa g;
+    if (!gopa_build(points, n, &g)) throw Error(VR_EINVAL, "vr_set_gradient_opacity: invalid map");
+    c->gopa_points.assign(points, points + n);
+    c->gopa = g;
 }
 
 void set_device(vr_ctx* c) { hip_check(hipSetDevice(c->device)); }
@@ -639,6 +655,10 @@ vr_ctx* create_common(const float* voxels, bool on_device, int64_t d1, int64_t d
         Colormap m;
         set_cmap(c.get(), ramp, colormap_build(ramp, 2, &m) ? 2 : 1);
     }
+    {   // VR_MODE_SCDVR starts with G == 1
+        const vr_gopa_point unit = {0.0f, 1.0f};
+        set_gopa(c.get(), &unit, 1);
+    }
     set_tf(c.get(), tf, n_tf);
     c->oct.build(d1, d2, d3);
     const int D = (int)c->oct.maximum_depth;
@@ -839,9 +859,9 @@ WorkCache* frame_list(vr_ctx* c, const vr_params* p, const vr_camera* cam, const
 #ifndef VR_TEST_AXIS_COLUMN_DEAL
 #define VR_TEST_AXIS_COLUMN_DEAL 0
 #endif
-    // (DVR, SDVR, CDVR, MIP and ISO frames: one general march for every view, its volume read like the corner volume)
+    // (DVR, SDVR, CDVR, SCDVR, MIP and ISO frames: one general march for every view, its volume read like the corner volume)
     const int deal = (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO ||
-                      p->mode == VR_MODE_SDVR || p->mode == VR_MODE_CDVR ||
+                      p->mode == VR_MODE_SDVR || mode_cmap(p) ||
                       (p->mode == VR_MODE_TEST && (VR_TEST_AXIS_COLUMN_DEAL || make_test(c, p, cam).axt < 0))) ? 1 : 0;
     std::vector<uint32_t> key = {(uint32_t)W, (uint32_t)H, (uint32_t)tx0, (uint32_t)tx1, (uint32_t)ty0, (uint32_t)ty1,
                                  (uint32_t)ma, (uint32_t)deal};
@@ -897,9 +917,9 @@ int hull_edges(const vr_ctx* c, const vr_params* p, const vr_camera* cam, float 
 // nothing can be visible, 2 when no claim can be made (TEST mode, opaque TF(0), a corner behind a
 // conic camera, a NaN camera), 1 with the points in xy.
 int project_box(const vr_ctx* c, const vr_params* p, const vr_camera* cam, double xy[8][2]) {
-    // (DVR, SDVR, CDVR, MIP, ISO: TEST's positions and in-volume test)
+    // (DVR, SDVR, CDVR, SCDVR, MIP, ISO: TEST's positions and in-volume test)
     if (p->mode == VR_MODE_TEST || p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO ||
-        p->mode == VR_MODE_SDVR || p->mode == VR_MODE_CDVR)
+        p->mode == VR_MODE_SDVR || mode_cmap(p))
         return project_box_test(c, p, cam, xy);
     if (p->mode != VR_MODE_VRC || !c->zero_transparent) return 2;
     double lo[3], hi[3];
@@ -943,7 +963,7 @@ int project_box(const vr_ctx* c, const vr_params* p, const vr_camera* cam, doubl
 // precision; the float matrices' rounding is far inside the 2-pixel margin visible_rect adds).
 // MIP and ISO frames: a ray without an in-volume sample is the background by definition, whatever TF(0) is.
 int project_box_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam, double xy[8][2]) {
-    // (CDVR: a sample outside the volume is C(0.0f), the colour map's own zero transparency)
+    // (CDVR, SCDVR: a sample outside the volume is C(0.0f), the colour map's own zero transparency)
     if (!mode_zero_transparent(c, p) && p->mode != VR_MODE_MIP && p->mode != VR_MODE_ISO) return 2;
     CameraState cs;
     cs.pos = {cam->pos[0], cam->pos[1], cam->pos[2]};
@@ -1197,7 +1217,7 @@ void check_params(const vr_params* p) {
     if (!p || p->width <= 0 || p->height <= 0 || p->samples_per_ray <= 0 || p->width > 65535 || p->height > 65535)
         throw Error(VR_EINVAL, "vr_params: bad width/height/samples_per_ray");
     if (p->mode != VR_MODE_VRC && p->mode != VR_MODE_TEST && p->mode != VR_MODE_DVR && p->mode != VR_MODE_MIP &&
-        p->mode != VR_MODE_ISO && p->mode != VR_MODE_SDVR && p->mode != VR_MODE_CDVR)
+        p->mode != VR_MODE_ISO && p->mode != VR_MODE_SDVR && p->mode != VR_MODE_CDVR && p->mode != VR_MODE_SCDVR)
         throw Error(VR_EINVAL, "vr_params: unknown mode");
     if (p->flags & ~(VR_FLAG_ESS | VR_FLAG_ERT | VR_FLAG_SHADE | VR_FLAG_CONIC))
         throw Error(VR_EINVAL, "vr_params: unknown flags");
@@ -1369,7 +1389,7 @@ TestFrame make_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam) {
     f.total = c->d[0] * c->d[1] * c->d[2];
     f.fd1 = (float)c->d[0]; f.fd2 = (float)c->d[1]; f.fd3 = (float)c->d[2];
     // (MIP, ISO: samples outside the volume take no part, so the clip and the culls hold for any TF)
-    // (CDVR: the colour map's C(0.0f).a == 0 in the interval TF's place)
+    // (CDVR, SCDVR: the colour map's C(0.0f).a == 0 in the interval TF's place)
     f.zero_transparent = (mode_zero_transparent(c, p) || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO) ? 1 : 0;
     f.cls0 = c->cls0_test;
     f.idx64 = (f.total + f.d2 * f.d3 + f.d3 + 1) >= ((int64_t)1 << 31) ? 1 : 0;
@@ -1656,7 +1676,7 @@ void ensure_dvr(vr_ctx* c) {
     }
 }
 
-// VR_MODE_CDVR's lazy state: ensure_dvr_volume and -- whenever the colour map changed -- its device
+// VR_MODE_CDVR's and VR_MODE_SCDVR's lazy state: ensure_dvr_volume and -- whenever the colour map changed -- its device
 // tables (the points' (x, inv) and colours, from the host table the law is evaluated with) and its
 // own cell bits over dvr_minmax.  Nothing here follows the interval TF, and nothing of DVR's follows
 // the colour map: a context that alternates the two modes rebuilds neither.
@@ -1865,7 +1885,8 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
     } else {
         const bool sdvr = p->mode == VR_MODE_SDVR;   // (DVR's state and frame, its own march)
         const bool dvr = p->mode == VR_MODE_DVR || sdvr, mip = p->mode == VR_MODE_MIP, iso = p->mode == VR_MODE_ISO;
-        const bool cdvr = p->mode == VR_MODE_CDVR;
+        const bool scdvr = p->mode == VR_MODE_SCDVR;   // (CDVR's state and frame, its own march)
+        const bool cdvr = p->mode == VR_MODE_CDVR || scdvr;
         if (dvr) ensure_dvr(c);
         else if (cdvr) ensure_cmap(c);
         else if (mip || iso) ensure_mip(c);   // (ISO reads MIP's bounds: a context that renders both builds them once)
@@ -1908,8 +1929,8 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             hip_check(launch_dvr_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8, c->dvr_start.as<float>(),
                                        c->dvr_seg.as<float4>(), c->dvr_occ.as<uint32_t>(), out, c->stream));
         } else if (cdvr) {
-            // the CDVR march: TEST's frame with DVR's cells under the colour map's own bits, plus the
-            // map's tables (ensure_cmap)
+            // the CDVR march, or SCDVR's over the same state: TEST's frame with DVR's cells under the colour
+            // map's own bits, plus the map's tables (ensure_cmap)
             const int64_t n = c->d[0] * c->d[1] * c->d[2];
             const bool u8 = c->dvr_u8_state == 1;
             f.axt = -1;
@@ -1919,10 +1940,23 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             f.occ_lds = (f.occ_words <= 8192 && c->occ_lds) ? 1 : 0;
             CmapFrame g = c->cmap_frame;
             g.vol_bytes = (int32_t)(u8 ? n + 16 : n * 4);   // (the byte copy: a dword at the last voxel stays inside)
-            // LDS budget, DVR's: the B table first, then the cell bits
+            // LDS budget, DVR's: the B table first, then the cell bits (SCDVR: over its own sum, G's table
+            // ahead of CDVR's carve-up)
             const bool ess = (f.flags & VR_FLAG_ESS) && f.zero_transparent;
-            if (cmap_lds_bytes(f, g, ess) > (size_t)kDvrLdsMax) f.sep_tab = 0;
-            if (cmap_lds_bytes(f, g, ess) > (size_t)kDvrLdsMax) f.occ_lds = 0;
+            const auto lds = [&] { return scdvr ? scdvr_lds_bytes(f, g, ess) : cmap_lds_bytes(f, g, ess); };
+            if (lds() > (size_t)kDvrLdsMax) f.sep_tab = 0;
+            if (lds() > (size_t)kDvrLdsMax) f.occ_lds = 0;
+            if (scdvr) {   // the Phong coefficients and G by value per frame, like ISO's
+                ScdvrFrame h;
+                h.ka = p->shade_ambient; h.kd = p->shade_diffuse; h.ks = p->shade_specular; h.shininess = p->shade_shininess;
+                h.n = c->gopa.n;
+                for (int i = 0; i < kMaxGopa; ++i) {
+                    h.m[i] = c->gopa.m[i]; h.inv[i] = c->gopa.inv[i]; h.w[i] = c->gopa.w[i];
+                }
+                hip_check(launch_scdvr_march(f, g, h, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8,
+                                             c->cmap_xi.as<float2>(), c->cmap_col.as<float4>(),
+                                             c->cmap_occ.as<uint32_t>(), out, c->stream));
+            } else
             hip_check(launch_cmap_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8, c->cmap_xi.as<float2>(),
                                         c->cmap_col.as<float4>(), c->cmap_occ.as<uint32_t>(), out, c->stream));
         } else if (mip) {
@@ -2336,6 +2370,31 @@ int vr_get_colormap(vr_ctx* c, vr_cmap_point* out, int32_t capacity, int32_t* n_
     *n_out = (int32_t)c->cmap_points.size();
     if ((size_t)capacity < c->cmap_points.size()) return VR_ERANGE;
     std::copy(c->cmap_points.begin(), c->cmap_points.end(), out);
+    return VR_OK;
+}
+
+// VR_MODE_SCDVR's gradient-opacity map: host state only, passed to the march by value per launch
+// (ScdvrFrame) like vr_set_isosurface's values, so nothing is rebuilt and queued frames keep the map
+// they were launched with.
+int vr_set_gradient_opacity(vr_ctx* c, const vr_gopa_point* points, int32_t n) {
+    if (!c || !points) return VR_EINVAL;
+    return guard([&] {
+        Gopa g;
+        if (!gopa_build(points, n, &g)) throw Error(VR_EINVAL, "vr_set_gradient_opacity: invalid map");
+        struct A { const vr_gopa_point* points; int n; } a{points, (int)n};
+        group_for_each(c, [](vr_ctx* pc, void* p) {
+            const A* x = static_cast<const A*>(p);
+            set_gopa(pc, x->points, x->n);
+        }, &a);
+        return VR_OK;
+    });
+}
+
+int vr_get_gradient_opacity(vr_ctx* c, vr_gopa_point* out, int32_t capacity, int32_t* n_out) {
+    if (!c || !out || !n_out || capacity < 0) return VR_EINVAL;
+    *n_out = (int32_t)c->gopa_points.size();
+    if ((size_t)capacity < c->gopa_points.size()) return VR_ERANGE;
+    std::copy(c->gopa_points.begin(), c->gopa_points.end(), out);
     return VR_OK;
 }
 
@@ -2771,7 +2830,7 @@ int vr_assemble_tiles(vr_ctx* c, int32_t W, int32_t H, int32_t tile_w, int32_t t
 int vr_count_samples(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64_t* n_in) {
     if (!c || !cam || !n_in) return VR_EINVAL;
     if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO || p->mode == VR_MODE_SDVR ||
-              p->mode == VR_MODE_CDVR))
+              mode_cmap(p)))
         return VR_EINVAL;   // (the counting passes cover VRC and TEST)
     return guard([&] {
         check_params(p);
@@ -2797,8 +2856,8 @@ int vr_count_samples(vr_ctx* c, const vr_params* p, const vr_camera* cam, uint64
 int vr_count_work(vr_ctx* c, const vr_params* p, const vr_camera* cam, vr_work_count* out) {
     if (!c || !cam || !out) return VR_EINVAL;
     if (p && (p->mode == VR_MODE_DVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO || p->mode == VR_MODE_SDVR ||
-              p->mode == VR_MODE_CDVR))
-        return VR_EINVAL;   // (no counting instantiation of the DVR, SDVR, CDVR, MIP and ISO marches)
+              mode_cmap(p)))
+        return VR_EINVAL;   // (no counting instantiation of the DVR, SDVR, CDVR, SCDVR, MIP and ISO marches)
     return guard([&] {
         check_params(p);
         set_device(c);

@@ -220,6 +220,21 @@ struct CmapFrame {
     float x[kCmapSmall];        // n <= kCmapSmall: x[0 .. n), the rest NaN (no value is >= NaN)
 };
 
+// The SCDVR march (vr_scdvr.hip) takes CDVR's TestFrame, CmapFrame and device tables unchanged and adds,
+// by value per launch like IsoFrame's (so vr_set_gradient_opacity between queued frames needs no
+// synchronisation): the Phong coefficients and the gradient-opacity map G (host/colormap.h).  The
+// march counts the m_i <= mag against the wave-uniform m and reads point max(j - 1, 0) from a
+// 16-entry LDS table {m_i, inv_i, w_i, w_{min(i + 1, n - 1)}} staged from these arguments.
+constexpr int kMaxGopa = 16;                 // VR_GOPA_MAX_POINTS
+constexpr int kGopaLds = kMaxGopa * 16;      // bytes of that table, ahead of CDVR's carve-up
+struct ScdvrFrame {
+    float ka, kd, ks, shininess;   // vr_params.shade_*
+    int32_t n;                  // points of G
+    float m[kMaxGopa];          // m[0 .. n), the rest NaN (no magnitude is >= NaN)
+    float inv[kMaxGopa];        // inv[i] = 1.0f / (m[i + 1] - m[i]), 0 from n - 1 on (never used)
+    float w[kMaxGopa];          // w[0 .. n), the rest w[n - 1]
+};
+
 // TransferFunction::getMaterial (TransferFunction.cu:46-55): last closed interval containing v, else 0
 __device__ __forceinline__ int tf_class(const float* lo, const float* hi, int n, float v) {
     int r = 0;

@@ -1,0 +1,436 @@
+// vr_scdvr.hip -- VR_MODE_SCDVR for gfx950: VR_MODE_CDVR's march (the trilinear sample under the
+// piecewise-linear RGBA colour map) with every non-transparent in-volume sample lit as VR_MODE_SDVR
+// lights it (the gradient of the trilinear field at the sample's own position, the two-sided headlight
+// Phong law) and its alpha scaled by the gradient-opacity map G of the gradient's magnitude
+// (include/vr_api.h, host/colormap.h).  Its own translation unit: cmap_march_kernel's text and
+// vr_sdvr.hip's single-sample helper and tap loop are restated here, so the device code of vr_cmap.hip
+// and vr_sdvr.hip stays what it is.  The mode reads CDVR's context state (tables, cell bits) only.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "vr_device.h"
+#include "vr_march.h"
+
+#pragma clang fp contract(off)
+
+namespace vr {
+
+// ------------------------------------------------------------------------------------------------
+// SCDVR march, one launch per frame: cmap_march_kernel's text (vr_cmap.hip; repeated rather than
+// shared) -- 16 x 16 rays per workgroup, work list / background workgroups / hull cull, TEST's
+// position chain with its per-frame B table in LDS, its clip and macro-cell jumps, batches of K = 4
+// samples whose positions and gathers are all issued before any is used, the byte and the float path,
+// the SMALL / LDS span search, the same LDS carve-up behind one more table.
+//
+// Added per ray: SDVR's headlight L = -(p(S - 1) - p(0)) / |.|.  Added per sample, once its colour
+// C(v) is known: the lanes whose sample is in the volume with alpha != 0 run six more single samples
+// of the field (scdvr_value_at) around the sample's position -- the tap loop rolled, as in
+// sdvr_march_kernel, so the batch's live gather registers are not multiplied by six -- and from the
+// central differences take len2, mag = sqrtf(len2), the weight G(mag) that scales the sample's alpha
+// and, with len2 > 0 and a light, the normal that goes through shade_normal.  A wave none of whose
+// lanes lights the sample skips all of it.
+//
+// G(mag): j = the number of m_i <= mag, a sum of kMaxGopa compares against the wave-uniform m (the
+// unused ones NaN: never <= mag; a NaN mag: 0); the point max(j - 1, 0) as {m, inv, w, w of the next
+// point} in one 16-byte LDS read from the table the workgroup's first lane stages from the kernel
+// arguments; flat tails (j == 0, j == n) give that point's w itself, otherwise the unfused lerp at
+// u = min((mag - m) * inv, 1) -- the law of the colour map with one channel.
+//
+// An alpha-0 sample is neither lit nor scaled: it stays the exact no-op of both blends that the
+// empty-cell skip (ESS, over CDVR's own cell bits) and the blank-batch skip rely on.
+// ------------------------------------------------------------------------------------------------
+constexpr int kScdvrK = 4;   // (= kCmapK: cmap_lds_bytes sizes the B table)
+
+// One sample of the field at a point inside the volume -- sdvr_value_at (vr_sdvr.hip) restated:
+// corners (int)p and min((int)p + 1, d - 1), weights p - (int)p, the gathers of the march (U8: four
+// unaligned dwords of the byte copy; else eight float gathers, a non-finite voxel reading as 0; the
+// edge clamp by selects), lerp1 in y, x, z.  Lanes with ok false issue no load and return 0.
+template <bool U8>
+__device__ __forceinline__ float scdvr_value_at(bool ok, float px, float py, float pz, __amdgpu_buffer_rsrc_t vrs,
+                                                int d3, int d23, int xl, int yl, int zl) {
+    const int ix = (int)px, iy = (int)py, iz = (int)pz;
+    const float dx = __builtin_amdgcn_fractf(px), dy = __builtin_amdgcn_fractf(py), dz = __builtin_amdgcn_fractf(pz);
+    const int base = ix * d23 + iy * d3 + iz;
+    const int ox = ix >= xl ? 0 : d23, oy = iy >= yl ? 0 : d3;
+    const bool lastz = iz >= zl;
+    int off[4];
+    off[0] = base;
+    off[1] = base + oy;
+    off[2] = base + ox;
+    off[3] = base + ox + oy;
+    uint32_t raw[U8 ? 4 : 8];
+#pragma unroll
+    for (int i = 0; i < (U8 ? 4 : 8); ++i) raw[i] = 0u;
+    if (ok) {
+        if (U8) {
+#pragma unroll
+            for (int xy = 0; xy < 4; ++xy) raw[xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy], 0, 0);
+        } else {
+            const int zs = lastz ? 0 : 4;
+#pragma unroll
+            for (int xy = 0; xy < 4; ++xy) {
+                raw[2 * xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy] * 4, 0, 0);
+                raw[2 * xy + 1] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy] * 4 + zs, 0, 0);
+            }
+        }
+    }
+    float c[8];   // corner kk = x << 2 | y << 1 | z
+#pragma unroll
+    for (int xy = 0; xy < 4; ++xy) {
+        if (U8) {
+            const uint32_t z0 = raw[xy] & 0xffu, z1 = (raw[xy] >> 8) & 0xffu;
+            c[2 * xy] = (float)z0;
+            c[2 * xy + 1] = (float)(lastz ? z0 : z1);
+        } else {
+#pragma unroll
+            for (int z = 0; z < 2; ++z) {   // a non-finite voxel reads as 0
+                const uint32_t u = raw[2 * xy + z];
+                c[2 * xy + z] = (u & 0x7f800000u) == 0x7f800000u ? 0.0f : __uint_as_float(u);
+            }
+        }
+    }
+    const float y1 = lerp1(c[0], c[2], dy), y2 = lerp1(c[1], c[3], dy);
+    const float y3 = lerp1(c[4], c[6], dy), y4 = lerp1(c[5], c[7], dy);
+    const float z1 = lerp1(y1, y3, dx), z2 = lerp1(y2, y4, dx);
+    return lerp1(z1, z2, dz);
+}
+
+// (No amdgpu_waves_per_eu cap: profiles/scdvr/resource_usage.txt -- every instantiation fits without
+// scratch left to itself.)
+template <bool F2B, bool ESS, bool U8, bool SMALL, bool SEP>
+__global__ __launch_bounds__(256) void scdvr_march_kernel(TestFrame f, CmapFrame g, ScdvrFrame h,
+                                                          const WorkTile* __restrict__ work,
+                                                          const void* __restrict__ vol,
+                                                          const float2* __restrict__ gxi,
+                                                          const float4* __restrict__ gcol,
+                                                          const uint32_t* __restrict__ gocc,
+                                                          float4* __restrict__ out) {
+    constexpr int K = kScdvrK;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
+    // LDS: G's points | then CDVR's carve-up: the points' colours | their (x, inv) | the cell bits
+    // (ESS) | the B table (SEP)
+    float4* s_G = reinterpret_cast<float4*>(smem_all);
+    unsigned char* smem = smem_all + kGopaLds;
+    float4* s_col = reinterpret_cast<float4*>(smem);
+    float2* s_xi = reinterpret_cast<float2*>(smem + (size_t)g.n * sizeof(float4));
+    const bool occ_st = ESS && f.occ_lds;
+    const size_t o_occ = (size_t)g.n * sizeof(float4) + ((size_t)g.n * sizeof(float2) + 15) / 16 * 16;
+    uint32_t* s_occ = reinterpret_cast<uint32_t*>(smem + o_occ);
+    float4* s_B = reinterpret_cast<float4*>(smem + o_occ + ((occ_st ? (size_t)f.occ_words * 4 : 0) + 15) / 16 * 16);
+    // first round of loads, unconditional (index clamped, value selected), as in cmap_march_kernel
+    const int ip = (int)threadIdx.x < g.n ? (int)threadIdx.x : 0;
+    const float4 cv = gcol[ip];
+    const float2 xv = gxi[ip];
+    asm volatile("" ::"s"(f.out_tiles), "s"(f.bg_first), "s"(f.n_work), "s"(f.n_hull), "s"(f.W), "s"(f.H));
+    uint32_t ov[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = (int)threadIdx.x + u * kWgThreads;
+        const bool io = occ_st && i < f.occ_words;
+        ov[u] = 0u;
+        if (ESS) { const uint32_t w = gocc[io ? i : 0]; ov[u] = io ? w : 0u; }
+    }
+    const int b = (int)blockIdx.x;
+    const WorkTile wt = work[b < f.n_work ? b : 0];
+    if (b >= f.n_work) return;
+    if (test_background(f, work, wt, out)) return;
+    if ((int)threadIdx.x < g.n) {
+        s_col[threadIdx.x] = cv;
+        s_xi[threadIdx.x] = xv;
+    }
+    // G's table from the kernel arguments: constant indices only (a lane-indexed read of a by-value
+    // struct would go through scratch), so one lane stores the 16 entries
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < kMaxGopa; ++i)
+            s_G[i] = make_float4(h.m[i], h.inv[i], h.w[i], h.w[i + 1 < kMaxGopa ? i + 1 : i]);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = (int)threadIdx.x + u * kWgThreads;
+        if (occ_st && i < f.occ_words) s_occ[i] = ov[u];
+    }
+    if (occ_st)
+        for (int i = threadIdx.x + 4 * kWgThreads; i < f.occ_words; i += kWgThreads) s_occ[i] = gocc[i];
+    if (SEP && f.sep_tab) test_stage_B(f, s_B, K);
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t ors = uniform_rsrc(gocc, ESS ? f.occ_words * 4 : 0);
+    auto occ_word = [&](int wi) -> uint32_t {
+        if (f.occ_lds) return s_occ[wi];
+        return __builtin_amdgcn_raw_buffer_load_b32(ors, wi * 4, 0, 0);
+    };
+    // the ERT threshold pinned in a VGPR (test_march_kernel)
+    float ert_eps = f.ert_eps;
+    asm volatile("" : "+v"(ert_eps));
+    int x, y;
+    ray_of_thread(wt, x, y);
+    if (x >= f.W || y >= f.H) return;
+
+    // TEST's position chain, clip and linear model (vr_march.h)
+    TestRay ray;
+    test_ray_init<SEP>(f, x, y, ray);
+    auto position = [&](int s, float p[3]) { test_position<SEP>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
+    int s_begin, s_end;
+    float pa[3], dp[3], idp[3];
+    float L[3] = {0.0f, 0.0f, 0.0f};
+    bool lit = false;   // the ray has a light direction
+    {
+        float pb[3];
+        position(0, pa);
+        position(f.S > 1 ? f.S - 1 : 0, pb);
+        test_clip(f, pa, pb, dp, idp, s_begin, s_end);
+        // headlight along the ray, in voxel space (sdvr_march_kernel's, from the same two end points)
+        const float ex = pb[0] - pa[0], ey = pb[1] - pa[1], ez = pb[2] - pa[2];
+        const float n2 = (ex * ex + ey * ey) + ez * ez;
+        if (n2 > 0.0f) {
+            const float il = 1.0f / sqrtf(n2);
+            L[0] = -ex * il; L[1] = -ey * il; L[2] = -ez * il;
+            lit = true;
+        }
+    }
+
+    const float4 c0 = make_float4(g.c0[0], g.c0[1], g.c0[2], g.c0[3]);
+    const int nl = g.n - 1;
+    // (host: the array is addressable with 32-bit byte offsets)
+    const int d3 = (int)f.d3, d23 = (int)(f.d2 * f.d3);
+    const int xl = (int)f.d1 - 1, yl = (int)f.d2 - 1, zl = (int)f.d3 - 1;
+    const __amdgpu_buffer_rsrc_t vrs = uniform_rsrc(vol, g.vol_bytes);
+    float r, gr, bl, T = 1.0f;
+    if (F2B) { r = 0.0f; gr = 0.0f; bl = 0.0f; }
+    else { r = f.bg[0]; gr = f.bg[1]; bl = f.bg[2]; }
+
+    int s = F2B ? s_begin : s_end - 1;
+    bool done = F2B ? (s >= s_end) : (s < s_begin);
+    float pfirst[3];   // ESS: the position of the batch's first sample, from the empty-cell test
+    while (!done) {
+        if (ESS) {
+            float* p = pfirst;
+            position(s, p);
+            // (bitwise, not short-circuit: && chains compile to exec-mask branches)
+            const bool inside = ((int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
+                                 (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
+                                 (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            int cc[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) cc[c] = inside ? ((int)p[c] >> f.tcb) : 0;
+            const int cell = __mul24(__mul24(cc[0], f.tnc[1]) + cc[1], f.tnc[2]) + cc[2];   // (< 2^18 cells)
+            if (inside && !((occ_word(cell >> 5) >> (cell & 31)) & 1u)) {
+                test_cell_jump<F2B>(f, cc, pa, dp, idp, s_begin, s_end, s, done);
+                continue;
+            }
+        }
+        float w[K][3];
+        bool in[K], lastz[K];
+        int off[K][4];
+        bool any_in = false;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int sk = F2B ? s + k : s - k;
+            const bool valid = F2B ? (sk < s_end) : (sk >= s_begin);
+            float p[3];
+            if (ESS && k == 0) {   // (s did not move since the empty-cell test: the same position)
+                p[0] = pfirst[0]; p[1] = pfirst[1]; p[2] = pfirst[2];
+            } else {
+                position(sk, p);
+            }
+            // 0 <= p < fd as unsigned compares of the bits (test_march_kernel)
+            in[k] = ((int)valid & (int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
+                     (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
+                     (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            any_in |= in[k];
+            int i0[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                i0[c] = (int)p[c];
+                // p - (float)(int)p: for an in-volume sample (p >= 0) that is p - floor(p), which
+                // v_fract_f32 returns exactly; outside, unused
+                w[k][c] = __builtin_amdgcn_fractf(p[c]);
+            }
+            // corner rows (x, y) at xy = x << 1 | y; the clamp to edge: no step at the last x / y
+            const int base = i0[0] * d23 + i0[1] * d3 + i0[2];
+            const int ox = i0[0] >= xl ? 0 : d23, oy = i0[1] >= yl ? 0 : d3;
+            off[k][0] = base;
+            off[k][1] = base + oy;
+            off[k][2] = base + ox;
+            off[k][3] = base + ox + oy;
+            lastz[k] = i0[2] >= zl;
+        }
+        // the gathers of the whole batch, exec-masked per sample (lanes outside skip them)
+        uint32_t raw[K][U8 ? 4 : 8];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            if (in[k]) {
+                if (U8) {
+#pragma unroll
+                    for (int xy = 0; xy < 4; ++xy) raw[k][xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy], 0, 0);
+                } else {
+                    const int zs = lastz[k] ? 0 : 4;
+#pragma unroll
+                    for (int xy = 0; xy < 4; ++xy) {
+                        raw[k][2 * xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4, 0, 0);
+                        raw[k][2 * xy + 1] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4 + zs, 0, 0);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < (U8 ? 4 : 8); ++i) raw[k][i] = 0u;
+            }
+        }
+        // a batch with every lane's samples outside the volume composites C(0) only: with C(0)
+        // transparent an exact no-op of either blend (f * (1 - 0) + c * 0 = f, T * (1 - 0) = T)
+        const bool blank = f.zero_transparent && !__any(any_in);
+        if (!blank) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                float c[8];   // corner kk = x << 2 | y << 1 | z
+#pragma unroll
+                for (int xy = 0; xy < 4; ++xy) {
+                    if (U8) {
+                        const uint32_t z0 = raw[k][xy] & 0xffu, z1 = (raw[k][xy] >> 8) & 0xffu;
+                        c[2 * xy] = (float)z0;
+                        c[2 * xy + 1] = (float)(lastz[k] ? z0 : z1);
+                    } else {
+#pragma unroll
+                        for (int z = 0; z < 2; ++z) {   // a non-finite voxel reads as 0
+                            const uint32_t u = raw[k][2 * xy + z];
+                            c[2 * xy + z] = (u & 0x7f800000u) == 0x7f800000u ? 0.0f : __uint_as_float(u);
+                        }
+                    }
+                }
+                const float dx = w[k][0], dy = w[k][1], dz = w[k][2];
+                const float y1 = lerp1(c[0], c[2], dy), y2 = lerp1(c[1], c[3], dy);
+                const float y3 = lerp1(c[4], c[6], dy), y4 = lerp1(c[5], c[7], dy);
+                const float z1 = lerp1(y1, y3, dx), z2 = lerp1(y2, y4, dx);
+                const float v = lerp1(z1, z2, dz);
+                int j = 0;   // the points x_i <= v (a NaN: none)
+                if (SMALL) {
+#pragma unroll
+                    for (int i = 0; i < kCmapSmall; ++i) j += (int)(v >= g.x[i]);
+                } else {
+#pragma unroll
+                    for (int step = kMaxCmap; step >= 1; step >>= 1) {
+                        const int np = j + step;
+                        const float xs = s_xi[min(np, g.n) - 1].x;
+                        j = (np <= g.n && v >= xs) ? np : j;
+                    }
+                }
+                const int ja = max(j - 1, 0), jb = min(j, nl);
+                const float2 xi = s_xi[ja];
+                const float4 ca = s_col[ja], cb = s_col[jb];
+                const float u = fminf((v - xi.x) * xi.y, 1.0f);
+                const float u1 = 1.0f - u;
+                const bool flat = ja == jb;   // below x_0, or from x_{n-1} on: the end colour itself
+                float4 cs;
+                cs.x = flat ? ca.x : ca.x * u1 + cb.x * u;
+                cs.y = flat ? ca.y : ca.y * u1 + cb.y * u;
+                cs.z = flat ? ca.z : ca.z * u1 + cb.z * u;
+                cs.w = flat ? ca.w : ca.w * u1 + cb.w * u;
+                float4 cf = in[k] ? cs : c0;
+                const int sk = F2B ? s + k : s - k;
+                // the lit samples: in the volume (in[k] holds the range test too) with alpha != 0
+                const bool sh = in[k] && cf.w != 0.0f;
+                if (__any(sh)) {
+                    float ps[3];
+                    position(sk, ps);   // (the batch kept the sample's fractions only: the same position again)
+                    // gradient of the trilinear field at p: taps t = 2 a (q+) and 2 a + 1 (q-) of axis a, both
+                    // in the volume for a lane that lights (selects, no indexed arrays: the loop is rolled)
+                    float gx = 0.0f, gy = 0.0f, gz = 0.0f, vplus = 0.0f;
+#pragma unroll 1
+                    for (int t = 0; t < 6; ++t) {
+                        const int a = t >> 1;
+                        const float pc = a == 0 ? ps[0] : (a == 1 ? ps[1] : ps[2]);
+                        const float top = (float)(a == 0 ? xl : (a == 1 ? yl : zl));
+                        const float qp = fminf(pc + 1.0f, top), qm = fmaxf(pc - 1.0f, 0.0f);
+                        const float q = (t & 1) ? qm : qp;
+                        const float tv = scdvr_value_at<U8>(sh, a == 0 ? q : ps[0], a == 1 ? q : ps[1],
+                                                            a == 2 ? q : ps[2], vrs, d3, d23, xl, yl, zl);
+                        if (t & 1) {
+                            const float span = qp - qm;
+                            const float ga = span > 0.0f ? (vplus - tv) / span : 0.0f;
+                            gx = a == 0 ? ga : gx;
+                            gy = a == 1 ? ga : gy;
+                            gz = a == 2 ? ga : gz;
+                        } else {
+                            vplus = tv;
+                        }
+                    }
+                    const float len2 = (gx * gx + gy * gy) + gz * gz;
+                    const float mag = sqrtf(len2);
+                    // gradient opacity G(mag), with or without a normal
+                    int jg = 0;   // the points m_i <= mag (a NaN: none)
+#pragma unroll
+                    for (int i = 0; i < kMaxGopa; ++i) jg += (int)(mag >= h.m[i]);
+                    const float4 ge = s_G[max(jg - 1, 0)];
+                    const float ug = fminf((mag - ge.x) * ge.y, 1.0f);
+                    const float ug1 = 1.0f - ug;
+                    const float gw = (jg == 0 || jg == h.n) ? ge.z : ge.z * ug1 + ge.w * ug;
+                    float4 nv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    if (lit && len2 > 0.0f) {   // (without a light direction: d = 1, spec = 0, as without a normal)
+                        const float inv = 1.0f / mag;
+                        nv = make_float4(-gx * inv, -gy * inv, -gz * inv, 1.0f);
+                        // two-sided: a normal facing away from the light is negated (exact), so the law's own
+                        // dot product is -ndl
+                        const float ndl = (nv.x * L[0] + nv.y * L[1]) + nv.z * L[2];
+                        if (ndl < 0.0f) { nv.x = -nv.x; nv.y = -nv.y; nv.z = -nv.z; }
+                    }
+                    float cr = cf.x, cg = cf.y, cb_ = cf.z;
+                    shade_normal(nv, L, h.ka, h.kd, h.ks, h.shininess, cr, cg, cb_);
+                    cf.x = sh ? cr : cf.x;
+                    cf.y = sh ? cg : cf.y;
+                    cf.z = sh ? cb_ : cf.z;
+                    cf.w = sh ? cf.w * gw : cf.w;
+                }
+                const float a = (F2B ? (sk < s_end) : (sk >= s_begin)) ? cf.w : 0.0f;
+                if (F2B) {
+                    const float wt_ = T * a;
+                    r = fmaf(wt_, cf.x, r); gr = fmaf(wt_, cf.y, gr); bl = fmaf(wt_, cf.z, bl);
+                    T = T * (1.0f - a);
+                } else {
+                    r = r * (1 - a) + cf.x * a;
+                    gr = gr * (1 - a) + cf.y * a;
+                    bl = bl * (1 - a) + cf.z * a;
+                }
+            }
+        }
+        if (F2B && T < ert_eps) done = true;
+        s = F2B ? s + K : s - K;
+        if (F2B ? (s >= s_end) : (s < s_begin)) done = true;
+    }
+    if (F2B) { r = r + T * f.bg[0]; gr = gr + T * f.bg[1]; bl = bl + T * f.bg[2]; }
+    store_pixel(out, out_index(f.out_tiles, wt, x, y, f.H, f.tile_w, f.tile_h), f.out_rgb, r, gr, bl);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Launch wrapper (called from vr_api.cpp)
+// ------------------------------------------------------------------------------------------------
+
+size_t cmap_lds_bytes(const TestFrame& f, const CmapFrame& g, bool ess);   // (vr_cmap.hip: the carve-up behind G's table)
+
+// LDS bytes of an SCDVR workgroup (host: CDVR's budget logic over this sum)
+size_t scdvr_lds_bytes(const TestFrame& f, const CmapFrame& g, bool ess) {
+    static_assert(kScdvrK == 4, "cmap_lds_bytes sizes the B table for batches of 4");
+    return (size_t)kGopaLds + cmap_lds_bytes(f, g, ess);
+}
+
+hipError_t launch_scdvr_march(const TestFrame& f, const CmapFrame& g, const ScdvrFrame& h, const WorkTile* work,
+                              int n_blocks, const void* vol, bool u8, const float2* xi, const float4* col,
+                              const uint32_t* occ, float4* out, hipStream_t st) {
+    const bool f2b = (f.flags & 2) != 0, ess = (f.flags & 1) != 0 && f.zero_transparent && occ != nullptr;
+    const bool small = g.n <= kCmapSmall, sep = f.sep != 0;
+    const size_t lds = scdvr_lds_bytes(f, g, ess);
+#define VR_C5(F2B_, ESS_, U8_, SMALL_, SEP_)                                                                       \
+    hipLaunchKernelGGL((scdvr_march_kernel<F2B_, ESS_, U8_, SMALL_, SEP_>), dim3(n_blocks), dim3(kWgThreads), lds, \
+                       st, f, g, h, work, vol, xi, col, occ, out)
+#define VR_C4(F2B_, ESS_, U8_, SMALL_) do { if (sep) VR_C5(F2B_, ESS_, U8_, SMALL_, true); else VR_C5(F2B_, ESS_, U8_, SMALL_, false); } while (0)
+#define VR_C3(F2B_, ESS_, U8_) do { if (small) VR_C4(F2B_, ESS_, U8_, true); else VR_C4(F2B_, ESS_, U8_, false); } while (0)
+#define VR_C2(F2B_, ESS_) do { if (u8) VR_C3(F2B_, ESS_, true); else VR_C3(F2B_, ESS_, false); } while (0)
+    if (f2b) { if (ess) VR_C2(true, true); else VR_C2(true, false); }
+    else { if (ess) VR_C2(false, true); else VR_C2(false, false); }
+#undef VR_C2
+#undef VR_C3
+#undef VR_C4
+#undef VR_C5
+    return hipGetLastError();
+}
+
+}  // namespace vr

@@ -28,6 +28,8 @@ VR_ISO_REFINE = 6     # its bisection rounds
 VR_MODE_SDVR = 9      # VR_MODE_DVR with every non-transparent in-volume sample lit (shade_*; no VR_FLAG_SHADE)
 VR_MODE_CDVR = 10     # VR_MODE_DVR under a piecewise-linear RGBA colour map (set_colormap; no TF)
 VR_CMAP_MAX_POINTS = 256
+VR_MODE_SCDVR = 11    # VR_MODE_CDVR lit like VR_MODE_SDVR, alpha scaled by G(|gradient|) (set_gradient_opacity)
+VR_GOPA_MAX_POINTS = 16
 VR_FLAG_ESS = 1
 VR_FLAG_ERT = 2
 VR_FLAG_SHADE = 8
@@ -50,6 +52,7 @@ EXPORTED = [
     "vr_render_batch", "vr_create_multi_ex", "vr_group_timing_read", "vr_count_work", "vr_group_traffic_read",
     "vr_axis_columns_plan", "vr_tf_segments", "vr_set_isosurface", "vr_get_isosurface",
     "vr_set_colormap", "vr_get_colormap", "vr_colormap_eval",
+    "vr_set_gradient_opacity", "vr_get_gradient_opacity", "vr_gradient_opacity_eval",
 ]
 VR_COMM_ID_BYTES = 128
 VR_TRANSPORT_NONE, VR_TRANSPORT_RCCL, VR_TRANSPORT_PEER_COPY = 0, 1, 2
@@ -90,6 +93,11 @@ class TFInterval(C.Structure):
 class CmapPoint(C.Structure):
     """vr_cmap_point: a control point of VR_MODE_CDVR's colour map, x in voxel units."""
     _fields_ = [("x", C.c_float), ("rgba", C.c_float * 4)]
+
+
+class GopaPoint(C.Structure):
+    """vr_gopa_point: a control point of VR_MODE_SCDVR's gradient-opacity map, m in voxel units per voxel."""
+    _fields_ = [("m", C.c_float), ("w", C.c_float)]
 
 
 class RenderParams(C.Structure):
@@ -185,6 +193,9 @@ def lib():
         "vr_set_colormap": ([vp, P(CmapPoint), C.c_int32], C.c_int),
         "vr_get_colormap": ([vp, P(CmapPoint), C.c_int32, P(C.c_int32)], C.c_int),
         "vr_colormap_eval": ([P(CmapPoint), C.c_int32, P(C.c_float), C.c_int64, P(C.c_float)], C.c_int),
+        "vr_set_gradient_opacity": ([vp, P(GopaPoint), C.c_int32], C.c_int),
+        "vr_get_gradient_opacity": ([vp, P(GopaPoint), C.c_int32, P(C.c_int32)], C.c_int),
+        "vr_gradient_opacity_eval": ([P(GopaPoint), C.c_int32, P(C.c_float), C.c_int64, P(C.c_float)], C.c_int),
         "vr_destroy": ([vp], C.c_int),
         "vr_render": ([vp, P(RenderParams), P(Camera), vp, C.c_int32], C.c_int),
         "vr_render_tiles": ([vp, P(RenderParams), P(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp,
@@ -290,10 +301,29 @@ def colormap_eval(points, v) -> np.ndarray:
     return out
 
 
+def _gopa_array(points):
+    pts = list(points)
+    arr = (GopaPoint * max(1, len(pts)))()
+    for i, (m, w) in enumerate(pts):
+        arr[i].m, arr[i].w = float(m), float(w)
+    return arr if pts else (GopaPoint * 0)()
+
+
+def gradient_opacity_eval(points, mag) -> np.ndarray:
+    """vr_gradient_opacity_eval: VR_MODE_SCDVR's gradient-opacity map G at the float32 magnitudes mag, on
+    the host (no GPU, no context), bit for bit what the march scales alpha with.  Returns mag.shape float32."""
+    arr = _gopa_array(points)
+    mm = np.ascontiguousarray(mag, np.float32)
+    out = np.empty(mm.shape, np.float32)
+    _check(lib().vr_gradient_opacity_eval(arr, len(arr), mm.ctypes.data_as(C.POINTER(C.c_float)), mm.size,
+                                          out.ctypes.data_as(C.POINTER(C.c_float))), "vr_gradient_opacity_eval")
+    return out
+
+
 def default_params(width, height, samples_per_ray, mode=VR_MODE_VRC, flags=0, ert_epsilon=1e-5) -> RenderParams:
-    """vr_params_default with the mode (VR_MODE_VRC, _TEST, _DVR, _MIP, _ISO, _SDVR or _CDVR), flags and ERT threshold
-    set.  VR_MODE_ISO and VR_MODE_SDVR always shade: they read shade_ambient / _diffuse / _specular /
-    _shininess without VR_FLAG_SHADE, which only VR_MODE_VRC accepts."""
+    """vr_params_default with the mode (VR_MODE_VRC, _TEST, _DVR, _MIP, _ISO, _SDVR, _CDVR or _SCDVR), flags and ERT
+    threshold set.  VR_MODE_ISO, VR_MODE_SDVR and VR_MODE_SCDVR always shade: they read shade_ambient /
+    _diffuse / _specular / _shininess without VR_FLAG_SHADE, which only VR_MODE_VRC accepts."""
     p = RenderParams()
     _check(lib().vr_params_default(width, height, samples_per_ray, C.byref(p)), "vr_params_default")
     p.mode, p.flags, p.ert_epsilon = mode, flags, ert_epsilon
@@ -532,6 +562,20 @@ class VolumeRenderer:
         arr, n = (CmapPoint * VR_CMAP_MAX_POINTS)(), C.c_int32()
         _check(lib().vr_get_colormap(self._ctx, arr, VR_CMAP_MAX_POINTS, C.byref(n)), "vr_get_colormap")
         return [(arr[i].x, tuple(arr[i].rgba)) for i in range(n.value)]
+
+    def set_gradient_opacity(self, points):
+        """VR_MODE_SCDVR's gradient-opacity map: a sequence of (m, w), m the gradient magnitude (voxel units
+        per voxel, strictly ascending), w in [0, 1] the factor on a lit sample's alpha.  Host state only:
+        each frame takes the map current when it is enqueued."""
+        arr = _gopa_array(points)
+        _check(lib().vr_set_gradient_opacity(self._ctx, arr, len(arr)), "vr_set_gradient_opacity")
+
+    @property
+    def gradient_opacity(self):
+        """[(m, w), ...] as the context holds them (float32)."""
+        arr, n = (GopaPoint * VR_GOPA_MAX_POINTS)(), C.c_int32()
+        _check(lib().vr_get_gradient_opacity(self._ctx, arr, VR_GOPA_MAX_POINTS, C.byref(n)), "vr_get_gradient_opacity")
+        return [(arr[i].m, arr[i].w) for i in range(n.value)]
 
     def render(self, params: RenderParams, camera: Camera) -> np.ndarray:
         """Host frame, shape (W, H, 4), x-major like the reference's screen buffer."""
