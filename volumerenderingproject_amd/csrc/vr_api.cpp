@@ -46,7 +46,7 @@ hipError_t launch_vrc_march(const VrcFrame&, const WorkTile*, const int32_t*, in
 hipError_t launch_vrc_columns(const VrcFrame*, int, int, const uint8_t*, const int32_t*, const float4*, int, float4*,
                               hipStream_t, int, const unsigned long long*, const int32_t*, int32_t*,
                               const VrcFrame* dev_frames = nullptr);
-hipError_t launch_axis_expand(const VrcFrame&, const WorkTile*, int, const float4*, float4*, hipStream_t);
+hipError_t launch_axis_expand(const VrcFrame&, const WorkTile*, int, int, int, const float4*, float4*, hipStream_t);
 size_t vrc_axis1_table_bytes(const VrcFrame&, int);
 int vrc_batch_of(const VrcFrame&, int);
 hipError_t launch_vrc_stats(const VrcFrame&, const WorkTile*, const int32_t*, int, const uint8_t*, const int32_t*,
@@ -1585,6 +1585,19 @@ VrcFrame column_frame(const VrcFrame& f, const ColumnPlan& cp) {
     return fc;
 }
 
+// The expand pass's split of a frame's work list (launch_axis_expand), apart from the march's n_launch:
+// a whole frame's list, its culled entries from bg_first on, goes kExpandGroup rectangle entries and
+// kExpandBgGroup culled ones to a workgroup; any other list (tile output, a persistent grid's, no
+// culled range) one entry to a workgroup, each storing the background itself where it is culled.
+struct ExpandGrid {
+    int rect_end, group, bg_group;
+};
+ExpandGrid expand_grid(const vr_ctx* c, const WorkView& wv, int out_tiles) {
+    if (!out_tiles && c->persist_wgs == 0 && wv.bg_first >= 0 && wv.bg_first <= wv.n_work)
+        return {wv.bg_first, kExpandGroup, kExpandBgGroup};
+    return {wv.n_work, 1, 1};
+}
+
 void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, WorkCache* wc, float4* out, int out_tiles,
                   int tile_w, int tile_h, int out_rgb, const TileRect* rect, const ColumnSlice* pre) {
     WorkView wv;
@@ -1854,7 +1867,8 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
         if (!pre && rect && !out_tiles && !out_rgb) cp = axis_columns_plan(c, p, f, *rect);
         if (pre) {   // the frame's columns are marched already (vr_render_batch, march_columns): expand only
             f.col_i0 = pre->i0; f.col_i1 = pre->i1; f.col_n0 = pre->n0; f.col_n1 = pre->n1;
-            hip_check(launch_axis_expand(f, wc->work, n_launch, pre->buf, out, c->stream));
+            const ExpandGrid eg = expand_grid(c, *wc, out_tiles);
+            hip_check(launch_axis_expand(f, wc->work, eg.rect_end, eg.group, eg.bg_group, pre->buf, out, c->stream));
         } else if (cp.take) {
             // column march into this stream's column buffer, then the expand pass, in stream order: the
             // next frame of the stream overwrites the buffer only after this frame's expand has read it.
@@ -1873,7 +1887,9 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
                                          (c->leafcols ? c->occ_leafcols : c->occ_cols).as<unsigned long long>(), gtab,
                                          gtab_out));
             f.col_i0 = cp.i0; f.col_i1 = cp.i1; f.col_n0 = cp.n0; f.col_n1 = cp.n1;
-            hip_check(launch_axis_expand(f, wc->work, n_launch, cb.as<float4>(), out, c->stream));
+            const ExpandGrid eg = expand_grid(c, *wc, out_tiles);
+            hip_check(launch_axis_expand(f, wc->work, eg.rect_end, eg.group, eg.bg_group, cb.as<float4>(), out,
+                                         c->stream));
         } else
         hip_check(launch_vrc_march(f, wc->work, nullptr, n_launch, vcls, vmaps,
                                    c->idx64 ? c->pmapx64.as<int64_t>() : nullptr, c->occ.as<uint32_t>(),

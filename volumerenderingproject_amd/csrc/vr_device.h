@@ -14,7 +14,22 @@ constexpr int kGeomOrtho = 0, kGeomAxis1 = 1, kGeomConic = 2, kGeomAxis1Run = 3,
 constexpr int kMaxTf = 256;
 constexpr int kLeafColsMax = 2048;   // leaf-column masks (AXIS1 ESS) up to this many leaves per axis
 constexpr int kBgGroup = 8;         // culled whole-frame work tiles stored per background-only workgroup
-constexpr int kCellDistCap = 16;   // cap of the ESS Chebyshev cell-distance field (relaxation steps)
+// the column path's expand pass (axis_expand_kernel): work tiles of the visible rectangle per workgroup,
+// culled work tiles per background-only workgroup, and its lane -> pixel mapping inside a tile
+// (0: ray_of_thread's 8 y per row, 1: 16).  -D knobs of the experiment builds only (tools/build_ab.sh)
+#ifndef VR_EXPAND_GROUP
+#define VR_EXPAND_GROUP 3
+#endif
+#ifndef VR_EXPAND_BG_GROUP
+#define VR_EXPAND_BG_GROUP 8
+#endif
+#ifndef VR_EXPAND_ROW16
+#define VR_EXPAND_ROW16 0
+#endif
+constexpr int kExpandGroup = VR_EXPAND_GROUP, kExpandBgGroup = VR_EXPAND_BG_GROUP, kExpandRow16 = VR_EXPAND_ROW16;
+static_assert(kExpandGroup >= 1 && kExpandGroup <= 8 && kExpandBgGroup >= 1 && kExpandBgGroup <= 16,
+              "the expand keeps a group's tiles and columns in registers");
+constexpr int kCellDistCap = 16;  // cap of the ESS Chebyshev cell-distance field (relaxation steps)
 constexpr int kMaxTabSamples = 8192;   // AXIS1 per-frame sample table (LDS) up to this many samples per ray
 constexpr int kMaxTestTab = 4096;      // TEST general views: per-frame B table (16 B per entry, <= 64 KB LDS)
 constexpr int kMaxHull = 8;         // edges of the projected dataset box's hull (workgroup cull)

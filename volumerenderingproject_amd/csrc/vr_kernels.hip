@@ -2029,44 +2029,128 @@ hipError_t launch_vrc_march(const VrcFrame& f, const WorkTile* work, const int32
 // list and background-only workgroups of the per-pixel march, its non-temporal float4 stores.  A
 // pixel outside the unit cube (or the rectangle: a culled tile's, by the host's bound) is the
 // background, exactly what the per-pixel march stores for a ray that is TF(0) throughout.
+//
+// A wave of this pass stores 1 KB per work tile and has nothing else to do: its life is a chain of
+// dependent round trips, and the fewer waves the pass needs to keep its stores going, the less it
+// gives way to a column march beside it.  Hence: every kernel argument is loaded
+// in the first round (the march's prologue idiom); a workgroup over the rectangle takes `group` <=
+// kExpandGroup consecutive work entries of [0, rect_end) -- all their work-tile loads issued
+// together, then all their column gathers, then the stores -- and a background-only workgroup
+// (blockIdx >= rect_wgs) `bg_group` <= kExpandBgGroup of the entries [rect_end, f.n_work), loaded
+// together ahead of the stores.  No load sits under a divergent branch or one of its own: an entry
+// past the end is a clamped load made a hole (a tile far off the frame), and a pixel that takes the
+// background gathers column 0 and drops it.  (expand_grid: the host's side of this.)
 // ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void expand_pixel(const WorkTile& wt, int& x, int& y) {
+    if constexpr (kExpandRow16) {   // 16 consecutive y per row: a wave stores 4 segments of 256 B
+        x = wt.x0 + (int)(threadIdx.x >> 4);
+        y = wt.y0 + (int)(threadIdx.x & 15);
+    } else {
+        ray_of_thread(wt, x, y);
+    }
+}
+
+// (one 16-byte store whatever the code around it: the four dword stores of store_f4 are merged by the
+// compiler only where no branch is shared between two of them)
+__device__ __forceinline__ void expand_store(float4* p, float4 v) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const f4 w = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(w, reinterpret_cast<f4*>(p));
+}
+
+// N work entries from e0 on, of which the first n below `end` count: clamped loads issued together, an
+// entry past the end made a hole (a tile far off the frame).  The list is read through the constant
+// address space (nothing writes it while the pass runs): behind an asm statement the compiler takes
+// global memory for clobbered and would load each tile with a vector load and a wait of its own.  The
+// asm here keeps the loads out of the selects that follow.
+typedef const __attribute__((address_space(4))) WorkTile* const_tiles;
+template <int N, bool SLOT>
+__device__ __forceinline__ void expand_tiles(const_tiles tiles, int e0, int n, int end, int* x0, int* y0, int* slot) {
+    const int last = max(end - 1, 0);
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const const_tiles w = tiles + min(e0 + i, last);
+        x0[i] = w->x0;
+        y0[i] = w->y0;
+        if constexpr (SLOT) slot[i] = w->slot;
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        if constexpr (SLOT) asm volatile("" ::"s"(x0[i]), "s"(y0[i]), "s"(slot[i]));
+        else asm volatile("" ::"s"(x0[i]), "s"(y0[i]));
+        if (!((i < n) & (e0 + i < end))) x0[i] = 1 << 30;
+    }
+}
+
 __global__ __launch_bounds__(256) void axis_expand_kernel(VrcFrame f, const WorkTile* __restrict__ work,
                                                           const float4* __restrict__ colbuf,
-                                                          float4* __restrict__ out) {
+                                                          float4* __restrict__ out, int rect_end, int rect_wgs,
+                                                          int group, int bg_group) {
+    // round 1: every kernel argument the pass reads, ahead of any branch on one
+    asm volatile("" ::"s"(f.W), "s"(f.H), "s"(f.rsw), "s"(f.rsh), "s"(f.leaves), "s"(f.axis1), "s"(f.nleaf),
+                 "s"(f.col_i0), "s"(f.col_i1), "s"(f.col_n0), "s"(f.col_n1), "s"(f.bg[0]), "s"(f.bg[1]), "s"(f.bg[2]),
+                 "s"((uint64_t)colbuf), "s"((uint64_t)out), "s"(f.tlc[0]), "s"(f.tlc[1]), "s"(f.tlc[2]), "s"(f.right[0]),
+                 "s"(f.right[1]), "s"(f.right[2]), "s"(f.up[0]), "s"(f.up[1]), "s"(f.up[2]), "s"(f.n_work), "s"(rect_end),
+                 "s"(bg_group), "s"(f.bg[3]));   // (bg[3]: or its register is reused by a load behind a wait of its own)
+    // round 2: the workgroup's work tiles (expand_tiles), background-only workgroups apart
+    const const_tiles tiles = (const_tiles)(uintptr_t)work;
+    const int b = (int)blockIdx.x;
     const float4 bg = make_float4(f.bg[0], f.bg[1], f.bg[2], 1.0f);
-    if ((int)blockIdx.x >= f.bg_first) {
-        const int e0 = f.bg_first + ((int)blockIdx.x - f.bg_first) * f.bg_group;
-        for (int i = 0; i < f.bg_group; ++i) {
-            const int e = e0 + i;
-            if (e >= f.n_work) break;
+    if (b >= rect_wgs) {
+        int x0[kExpandBgGroup], y0[kExpandBgGroup];
+        expand_tiles<kExpandBgGroup, false>(tiles, rect_end + (b - rect_wgs) * bg_group, bg_group, f.n_work, x0, y0,
+                                            nullptr);
+#pragma unroll
+        for (int i = 0; i < kExpandBgGroup; ++i) {
             int x, y;
-            ray_of_thread(work[e], x, y);
-            if (x < f.W && y < f.H) store_f4(out + (int64_t)x * f.H + y, bg);
+            expand_pixel(WorkTile{x0[i], y0[i], 0, 0}, x, y);
+            if (x < f.W && y < f.H) expand_store(out + (int64_t)x * f.H + y, bg);
         }
         return;
     }
-    if ((int)blockIdx.x >= f.n_work) return;
-    const WorkTile wt = work[blockIdx.x];
-    int x, y;
-    ray_of_thread(wt, x, y);
-    if (!(x < f.W && y < f.H)) return;   // (a hole of the dealt list lies far off the frame)
-    float4 v = bg;
-    if (wt.slot >= 0) {
+    int x0[kExpandGroup], y0[kExpandGroup], slot[kExpandGroup];
+    expand_tiles<kExpandGroup, true>(tiles, b * group, group, rect_end, x0, y0, slot);
+    float4 v[kExpandGroup];
+    bool hit[kExpandGroup];
+#pragma unroll
+    for (int i = 0; i < kExpandGroup; ++i) {
+        int x, y;
+        expand_pixel(WorkTile{x0[i], y0[i], 0, 0}, x, y);
         float P0[3];
         int i0, i1;
         bool in_cube;
         ray_origin(f, x, y, P0);
         axis_leaf_column(f, f.axis1, P0, i0, i1, in_cube);
         const unsigned c0 = (unsigned)(i0 - f.col_i0), c1 = (unsigned)(i1 - f.col_i1);
-        if (in_cube && c0 < (unsigned)f.col_n0 && c1 < (unsigned)f.col_n1) v = colbuf[c0 * (unsigned)f.col_n1 + c1];
+        // (a hole of the dealt list lies far off the frame; a culled tile's pixels are the background)
+        hit[i] = (x < f.W) & (y < f.H) & (slot[i] >= 0) & in_cube & (c0 < (unsigned)f.col_n0) &
+                 (c1 < (unsigned)f.col_n1);
+        v[i] = colbuf[hit[i] ? c0 * (unsigned)f.col_n1 + c1 : 0u];
     }
-    store_f4(out + (int64_t)x * f.H + y, v);
+    // round 3: the gathers, all in flight (or the compiler sinks a gather into its store's branch)
+#pragma unroll
+    for (int i = 0; i < kExpandGroup; ++i) asm volatile("" ::"v"(v[i].x), "v"(v[i].y), "v"(v[i].z), "v"(v[i].w));
+#pragma unroll
+    for (int i = 0; i < kExpandGroup; ++i) {
+        int x, y;
+        expand_pixel(WorkTile{x0[i], y0[i], 0, 0}, x, y);
+        if (x < f.W && y < f.H) expand_store(out + (int64_t)x * f.H + y, hit[i] ? v[i] : bg);
+    }
 }
 
-hipError_t launch_axis_expand(const VrcFrame& f, const WorkTile* work, int n_blocks, const float4* colbuf, float4* out,
-                              hipStream_t st) {
+// The expand's grid over a work list whose entries [0, rect_end) are the visible rectangle's and
+// [rect_end, f.n_work) background only: ceil(rect_end / group) workgroups, then ceil of the rest /
+// bg_group.  Any group sizes from 1 up to the kernel's constants are correct.
+hipError_t launch_axis_expand(const VrcFrame& f, const WorkTile* work, int rect_end, int group, int bg_group,
+                              const float4* colbuf, float4* out, hipStream_t st) {
+    if (rect_end < 0 || rect_end > f.n_work || group < 1 || group > kExpandGroup || bg_group < 1 ||
+        bg_group > kExpandBgGroup || !colbuf)
+        return hipErrorInvalidValue;
+    const int rect_wgs = (rect_end + group - 1) / group;
+    const int n_blocks = rect_wgs + (f.n_work - rect_end + bg_group - 1) / bg_group;
     if (n_blocks <= 0) return hipSuccess;
-    hipLaunchKernelGGL(axis_expand_kernel, dim3(n_blocks), dim3(kWgThreads), 0, st, f, work, colbuf, out);
+    hipLaunchKernelGGL(axis_expand_kernel, dim3(n_blocks), dim3(kWgThreads), 0, st, f, work, colbuf, out, rect_end,
+                       rect_wgs, group, bg_group);
     return hipGetLastError();
 }
 
