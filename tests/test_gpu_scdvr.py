@@ -1,4 +1,4 @@
-"""VR_MODE_SCDVR on the GPU (scdvr_march_kernel): VR_MODE_CDVR's sample under the colour map, lit as
+"""VR_MODE_SCDVR on the GPU (cmap_march_kernel, SHADE): VR_MODE_CDVR's sample under the colour map, lit as
 VR_MODE_SDVR lights and with its alpha scaled by the gradient-opacity map G, held to the numpy restatement
 tests/scdvr_ref.py (itself held to vr_gradient_opacity_eval and to the CDVR and SDVR restatements by
 tests/test_scdvr_ref.py, which also shows that the cases of tests/scdvr_cases.py bite).
@@ -174,7 +174,7 @@ def test_margin_case():
 
 
 def scdvr_lds(n, cell_bits, S):
-    """scdvr_lds_bytes (vr_scdvr.hip) restated: G's 16 points of 16 B, then cmap_lds_bytes."""
+    """cmap_lds_bytes (vr_cmap.hip) with shade restated: G's 16 points of 16 B, then CDVR's carve-up."""
     return 256 + n * 16 + (n * 8 + 15) // 16 * 16 + (cell_bits + 15) // 16 * 16 + (S + 8) * 16
 
 

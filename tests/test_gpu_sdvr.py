@@ -1,4 +1,4 @@
-"""VR_MODE_SDVR on the GPU (sdvr_march_kernel): VR_MODE_DVR with every non-transparent in-volume sample
+"""VR_MODE_SDVR on the GPU (dvr_march_kernel, SHADE): VR_MODE_DVR with every non-transparent in-volume sample
 lit by the gradient of the trilinear field, held to the numpy restatement tests/sdvr_ref.py (itself held
 to the DVR and ISO restatements and to a closed form by tests/test_sdvr_ref.py, which also shows that the
 cases of tests/sdvr_cases.py bite).

@@ -209,7 +209,7 @@ struct vr_ctx {
     // (cleared when the classes change)
     mutable std::map<std::vector<uint32_t>, std::vector<int32_t>> vis_cache;
     bool cls_test_valid = false;
-    // VR_MODE_DVR (vr_dvr.hip) and VR_MODE_SDVR (vr_sdvr.hip, which adds nothing), built on the first
+    // VR_MODE_DVR and VR_MODE_SDVR (vr_dvr.hip; the shaded march adds nothing), built on the first
     // frame of either: the byte copy of the volume (dvr_u8_state
     // 0 = not tried, 1 = built and lossless, 2 = the volume is not bytes / the option forbids it), the
     // min/max of the cells (2^dvr_tcb voxels per axis), and -- rebuilt when the TF changes (dvr_tf_valid)
@@ -241,7 +241,7 @@ struct vr_ctx {
     bool cmap_valid = false;
     vr::DevBuf cmap_xi, cmap_col, cmap_occ;
     vr::CmapFrame cmap_frame{};
-    // VR_MODE_SCDVR (vr_scdvr.hip) reads the CDVR state above and adds host state only: the
+    // VR_MODE_SCDVR (vr_cmap.hip, the shaded march) reads the CDVR state above and adds host state only: the
     // gradient-opacity map as the caller gave it and as the law reads it (host/colormap.h; create: the
     // single point (0, 1)), set by vr_set_gradient_opacity and passed to the march by value per launch
     std::vector<vr_gopa_point> gopa_points;

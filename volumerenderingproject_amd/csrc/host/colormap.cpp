@@ -1,7 +1,7 @@
 // colormap.cpp -- the colour map of VR_MODE_CDVR and the gradient-opacity map of VR_MODE_SCDVR on the
 // host (colormap.h), vr_colormap_eval and vr_gradient_opacity_eval.
-// Compiled without FP contraction (Makefile FPFLAGS): the device marches (vr_cmap.hip, vr_scdvr.hip)
-// evaluate the same expressions from the same x / inv / value tables, so the two agree bit for bit.
+// Compiled without FP contraction (Makefile FPFLAGS): the device march (vr_cmap.hip, with and without SHADE)
+// evaluates the same expressions from the same x / inv / value tables, so the two agree bit for bit.
 #include "colormap.h"
 
 #include <cmath>

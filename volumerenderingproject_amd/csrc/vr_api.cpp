@@ -68,8 +68,8 @@ hipError_t launch_test_march(const TestFrame&, const WorkTile*, const int32_t*, 
                              const int32_t*, unsigned long long*, const int32_t*, int);
 hipError_t launch_test_occupancy(const uint8_t*, int64_t, int64_t, int64_t, int, int, int, int, const uint8_t*,
                                  unsigned long long*, hipStream_t);
-hipError_t launch_dvr_march(const TestFrame&, const DvrFrame&, const WorkTile*, int, const void*, bool, const float*,
-                            const float4*, const uint32_t*, float4*, hipStream_t);
+hipError_t launch_dvr_march(const TestFrame&, const DvrFrame&, const SdvrFrame*, const WorkTile*, int, const void*, bool,
+                            const float*, const float4*, const uint32_t*, float4*, hipStream_t);
 size_t dvr_lds_bytes(const TestFrame&, const DvrFrame&, bool);
 hipError_t launch_dvr_bytes(const float*, int64_t, uint8_t*, int32_t*, hipStream_t);
 hipError_t launch_dvr_minmax(const float*, int64_t, int64_t, int64_t, int, int, int, int, float2*, hipStream_t);
@@ -79,15 +79,10 @@ hipError_t launch_mip_march(const TestFrame&, const MipFrame&, const WorkTile*, 
 hipError_t launch_mip_bounds(const float2*, int64_t, float*, hipStream_t);
 hipError_t launch_iso_march(const TestFrame&, const IsoFrame&, const WorkTile*, int, const void*, bool, const float*,
                             float4*, hipStream_t);
-hipError_t launch_sdvr_march(const TestFrame&, const DvrFrame&, const SdvrFrame&, const WorkTile*, int, const void*, bool,
-                             const float*, const float4*, const uint32_t*, float4*, hipStream_t);
-hipError_t launch_cmap_march(const TestFrame&, const CmapFrame&, const WorkTile*, int, const void*, bool, const float2*,
-                             const float4*, const uint32_t*, float4*, hipStream_t);
-size_t cmap_lds_bytes(const TestFrame&, const CmapFrame&, bool);
+hipError_t launch_cmap_march(const TestFrame&, const CmapFrame&, const ScdvrFrame*, const WorkTile*, int, const void*, bool,
+                             const float2*, const float4*, const uint32_t*, float4*, hipStream_t);
+size_t cmap_lds_bytes(const TestFrame&, const CmapFrame&, bool, bool);
 hipError_t launch_cmap_cells(const float2*, int64_t, const float2*, const float4*, int, unsigned long long*, hipStream_t);
-hipError_t launch_scdvr_march(const TestFrame&, const CmapFrame&, const ScdvrFrame&, const WorkTile*, int, const void*, bool,
-                              const float2*, const float4*, const uint32_t*, float4*, hipStream_t);
-size_t scdvr_lds_bytes(const TestFrame&, const CmapFrame&, bool);
 static_assert(kMaxGopa == VR_GOPA_MAX_POINTS, "vr_device.h and vr_api.h disagree on the gradient-opacity map's size");
 static_assert(kMaxCmap == VR_CMAP_MAX_POINTS, "vr_device.h and vr_api.h disagree on the colour map's size");
 static_assert(kIsoRefine == VR_ISO_REFINE, "vr_device.h and vr_api.h disagree on the refinement rounds");
@@ -1758,6 +1753,40 @@ void ensure_normals(vr_ctx* c, const vr_params* p) {
     }
 }
 
+// What the field modes' frames (DVR / SDVR, CDVR / SCDVR, MIP, ISO) share: one general march for every
+// view over DVR's min/max cells (the cell-bit fields are read by the marches that have cell bits), its
+// corner gathers reading the byte copy of the volume when there is one
+struct FieldVolume {
+    const void* p;
+    bool u8;
+    int32_t bytes;   // the gathers' buffer bound
+};
+FieldVolume field_frame(const vr_ctx* c, TestFrame& f) {
+    f.axt = -1;
+    f.tcb = c->dvr_tcb;
+    for (int a = 0; a < 3; ++a) f.tnc[a] = c->dvr_tnc[a];
+    f.occ_words = (int)(((int64_t)f.tnc[0] * f.tnc[1] * f.tnc[2] + 31) / 32);
+    f.occ_lds = (f.occ_words <= 8192 && c->occ_lds) ? 1 : 0;
+    const int64_t n = c->d[0] * c->d[1] * c->d[2];
+    const bool u8 = c->dvr_u8_state == 1;
+    // (the byte copy: a dword at the last voxel stays inside)
+    return {u8 ? c->dvr_u8.p : c->vol.p, u8, (int32_t)(u8 ? n + 16 : n * 4)};
+}
+
+// LDS budget of a DVR or CDVR workgroup: the B table goes first (its entries are then computed per
+// sample, the same expressions), then the cell bits (read through the cache instead)
+template <class LdsBytes>
+void fit_lds(TestFrame& f, LdsBytes lds_bytes) {
+    if (lds_bytes() > (size_t)kDvrLdsMax) f.sep_tab = 0;
+    if (lds_bytes() > (size_t)kDvrLdsMax) f.occ_lds = 0;
+}
+
+// vr_params.shade_* into the frame of a mode that always shades (IsoFrame, SdvrFrame, ScdvrFrame)
+template <class Frame>
+void set_phong(Frame& h, const vr_params* p) {
+    h.ka = p->shade_ambient; h.kd = p->shade_diffuse; h.ks = p->shade_specular; h.shininess = p->shade_shininess;
+}
+
 void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const WorkView& wv, float4* out, int out_tiles,
                   int tile_w, int tile_h, int out_rgb, const TileRect* rect, const ColumnSlice* pre) {
     const WorkView* wc = &wv;
@@ -1899,9 +1928,9 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
                                    c->cdist_p, gtab, gtab_out, c->count_ptr));
         if (gtab_out) c->axtab[c->stream].key = std::move(pub_key);   // valid for later launches on this stream
     } else {
-        const bool sdvr = p->mode == VR_MODE_SDVR;   // (DVR's state and frame, its own march)
+        const bool sdvr = p->mode == VR_MODE_SDVR;   // (DVR's state, frame and march, shaded)
         const bool dvr = p->mode == VR_MODE_DVR || sdvr, mip = p->mode == VR_MODE_MIP, iso = p->mode == VR_MODE_ISO;
-        const bool scdvr = p->mode == VR_MODE_SCDVR;   // (CDVR's state and frame, its own march)
+        const bool scdvr = p->mode == VR_MODE_SCDVR;   // (CDVR's state, frame and march, shaded)
         const bool cdvr = p->mode == VR_MODE_CDVR || scdvr;
         if (dvr) ensure_dvr(c);
         else if (cdvr) ensure_cmap(c);
@@ -1920,93 +1949,55 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             n_launch = wc->bg_first + (wc->n_work - wc->bg_first + kBgGroup - 1) / kBgGroup;
         }
         if (dvr) {
-            // the DVR march: TEST's frame with its own cells, plus the TF's segments (ensure_dvr)
-            const int64_t n = c->d[0] * c->d[1] * c->d[2];
-            const bool u8 = c->dvr_u8_state == 1;
-            f.axt = -1;
-            f.tcb = c->dvr_tcb;
-            for (int a = 0; a < 3; ++a) f.tnc[a] = c->dvr_tnc[a];
-            f.occ_words = (int)(((int64_t)f.tnc[0] * f.tnc[1] * f.tnc[2] + 31) / 32);
-            f.occ_lds = (f.occ_words <= 8192 && c->occ_lds) ? 1 : 0;
+            // the DVR march, or SDVR's (its SHADE variant): TEST's frame with its own cells, plus the TF's
+            // segments (ensure_dvr)
+            const FieldVolume v = field_frame(c, f);
             DvrFrame g = c->dvr_frame;
-            g.vol_bytes = (int32_t)(u8 ? n + 16 : n * 4);   // (the byte copy: a dword at the last voxel stays inside)
-            // LDS budget: the B table first (its entries are then computed per sample, the same
-            // expressions), then the cell bits (read through the cache instead)
+            g.vol_bytes = v.bytes;
             const bool ess = (f.flags & VR_FLAG_ESS) && f.zero_transparent;
-            if (dvr_lds_bytes(f, g, ess) > (size_t)kDvrLdsMax) f.sep_tab = 0;
-            if (dvr_lds_bytes(f, g, ess) > (size_t)kDvrLdsMax) f.occ_lds = 0;
-            if (sdvr) {   // the Phong coefficients by value per frame, like ISO's
-                SdvrFrame h;
-                h.ka = p->shade_ambient; h.kd = p->shade_diffuse; h.ks = p->shade_specular; h.shininess = p->shade_shininess;
-                hip_check(launch_sdvr_march(f, g, h, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8,
-                                            c->dvr_start.as<float>(), c->dvr_seg.as<float4>(),
-                                            c->dvr_occ.as<uint32_t>(), out, c->stream));
-            } else
-            hip_check(launch_dvr_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8, c->dvr_start.as<float>(),
+            fit_lds(f, [&] { return dvr_lds_bytes(f, g, ess); });
+            SdvrFrame h;   // SDVR: the Phong coefficients by value per frame, like ISO's
+            set_phong(h, p);
+            hip_check(launch_dvr_march(f, g, sdvr ? &h : nullptr, wc->work, n_launch, v.p, v.u8, c->dvr_start.as<float>(),
                                        c->dvr_seg.as<float4>(), c->dvr_occ.as<uint32_t>(), out, c->stream));
         } else if (cdvr) {
-            // the CDVR march, or SCDVR's over the same state: TEST's frame with DVR's cells under the colour
+            // the CDVR march, or SCDVR's (its SHADE variant): TEST's frame with DVR's cells under the colour
             // map's own bits, plus the map's tables (ensure_cmap)
-            const int64_t n = c->d[0] * c->d[1] * c->d[2];
-            const bool u8 = c->dvr_u8_state == 1;
-            f.axt = -1;
-            f.tcb = c->dvr_tcb;
-            for (int a = 0; a < 3; ++a) f.tnc[a] = c->dvr_tnc[a];
-            f.occ_words = (int)(((int64_t)f.tnc[0] * f.tnc[1] * f.tnc[2] + 31) / 32);
-            f.occ_lds = (f.occ_words <= 8192 && c->occ_lds) ? 1 : 0;
+            const FieldVolume v = field_frame(c, f);
             CmapFrame g = c->cmap_frame;
-            g.vol_bytes = (int32_t)(u8 ? n + 16 : n * 4);   // (the byte copy: a dword at the last voxel stays inside)
-            // LDS budget, DVR's: the B table first, then the cell bits (SCDVR: over its own sum, G's table
-            // ahead of CDVR's carve-up)
+            g.vol_bytes = v.bytes;
             const bool ess = (f.flags & VR_FLAG_ESS) && f.zero_transparent;
-            const auto lds = [&] { return scdvr ? scdvr_lds_bytes(f, g, ess) : cmap_lds_bytes(f, g, ess); };
-            if (lds() > (size_t)kDvrLdsMax) f.sep_tab = 0;
-            if (lds() > (size_t)kDvrLdsMax) f.occ_lds = 0;
-            if (scdvr) {   // the Phong coefficients and G by value per frame, like ISO's
-                ScdvrFrame h;
-                h.ka = p->shade_ambient; h.kd = p->shade_diffuse; h.ks = p->shade_specular; h.shininess = p->shade_shininess;
-                h.n = c->gopa.n;
-                for (int i = 0; i < kMaxGopa; ++i) {
-                    h.m[i] = c->gopa.m[i]; h.inv[i] = c->gopa.inv[i]; h.w[i] = c->gopa.w[i];
-                }
-                hip_check(launch_scdvr_march(f, g, h, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8,
-                                             c->cmap_xi.as<float2>(), c->cmap_col.as<float4>(),
-                                             c->cmap_occ.as<uint32_t>(), out, c->stream));
-            } else
-            hip_check(launch_cmap_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8, c->cmap_xi.as<float2>(),
+            fit_lds(f, [&] { return cmap_lds_bytes(f, g, ess, scdvr); });   // (SCDVR: G's table counts)
+            ScdvrFrame h;   // SCDVR: the Phong coefficients and G by value per frame, like ISO's
+            set_phong(h, p);
+            h.n = c->gopa.n;
+            for (int i = 0; i < kMaxGopa; ++i) {
+                h.m[i] = c->gopa.m[i]; h.inv[i] = c->gopa.inv[i]; h.w[i] = c->gopa.w[i];
+            }
+            hip_check(launch_cmap_march(f, g, scdvr ? &h : nullptr, wc->work, n_launch, v.p, v.u8, c->cmap_xi.as<float2>(),
                                         c->cmap_col.as<float4>(), c->cmap_occ.as<uint32_t>(), out, c->stream));
         } else if (mip) {
             // the MIP march: TEST's frame with DVR's cells, plus the cells' bounds (ensure_mip)
-            const int64_t n = c->d[0] * c->d[1] * c->d[2];
-            const bool u8 = c->dvr_u8_state == 1;
-            f.axt = -1;
-            f.tcb = c->dvr_tcb;
-            for (int a = 0; a < 3; ++a) f.tnc[a] = c->dvr_tnc[a];
+            const FieldVolume v = field_frame(c, f);
             MipFrame g;
             std::memset(&g, 0, sizeof g);
             g.cal_max = c->cal_max;
             g.vol_bound = c->mip_vol_bound;
-            g.vol_bytes = (int32_t)(u8 ? n + 16 : n * 4);   // (the byte copy: a dword at the last voxel stays inside)
+            g.vol_bytes = v.bytes;
             g.bound_bytes = (int32_t)((int64_t)f.tnc[0] * f.tnc[1] * f.tnc[2] * 4);   // (<= 2^18 cells)
-            hip_check(launch_mip_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8,
-                                       c->mip_bound.as<float>(), out, c->stream));
+            hip_check(launch_mip_march(f, g, wc->work, n_launch, v.p, v.u8, c->mip_bound.as<float>(), out, c->stream));
         } else if (iso) {
             // the ISO march: MIP's frame and bounds, plus the isovalue, the colour and the Phong
             // coefficients by value (vr_set_isosurface between queued frames touches no device state)
-            const int64_t n = c->d[0] * c->d[1] * c->d[2];
-            const bool u8 = c->dvr_u8_state == 1;
-            f.axt = -1;
-            f.tcb = c->dvr_tcb;
-            for (int a = 0; a < 3; ++a) f.tnc[a] = c->dvr_tnc[a];
+            const FieldVolume v = field_frame(c, f);
             IsoFrame g;
             std::memset(&g, 0, sizeof g);
             g.iso = c->iso_value;
             for (int a = 0; a < 3; ++a) g.rgb[a] = c->iso_rgb[a];
-            g.ka = p->shade_ambient; g.kd = p->shade_diffuse; g.ks = p->shade_specular; g.shininess = p->shade_shininess;
-            g.vol_bytes = (int32_t)(u8 ? n + 16 : n * 4);   // (the byte copy: a dword at the last voxel stays inside)
+            set_phong(g, p);
+            g.vol_bytes = v.bytes;
             g.bound_bytes = (int32_t)((int64_t)f.tnc[0] * f.tnc[1] * f.tnc[2] * 4);   // (<= 2^18 cells)
-            hip_check(launch_iso_march(f, g, wc->work, n_launch, u8 ? c->dvr_u8.p : c->vol.p, u8,
-                                       c->mip_bound.as<float>(), out, c->stream));
+            hip_check(launch_iso_march(f, g, wc->work, n_launch, v.p, v.u8, c->mip_bound.as<float>(), out, c->stream));
         } else {
         // axis views: the march axis's tables built here once per view and staged by every workgroup
         // (per stream, like the VRC view tables; a new view first drains the launches of this stream)

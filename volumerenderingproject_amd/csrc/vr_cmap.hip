@@ -1,8 +1,10 @@
 // vr_cmap.hip -- VR_MODE_CDVR for gfx950: VR_MODE_DVR's trilinear sample of the scalar field
 // classified by a piecewise-linear RGBA colour map (include/vr_api.h, host/colormap.h) instead of
-// the interval transfer function, and the empty-cell bits that follow that map.  Its own translation
-// unit: the sample block of dvr_march_kernel is restated here (as vr_mip.hip, vr_iso.hip and
-// vr_sdvr.hip do), so vr_dvr.hip's device code stays what it is.
+// the interval transfer function, and the empty-cell bits that follow that map; VR_MODE_SCDVR is the
+// same march with every non-transparent in-volume sample lit and its alpha scaled by the
+// gradient-opacity map G (the kernel's SHADE flag).  Its own translation unit: the sample block of
+// dvr_march_kernel is restated here (as vr_mip.hip and vr_iso.hip do), so vr_dvr.hip's device code
+// stays what it is.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,19 +36,42 @@ namespace vr {
 //
 // ESS: cells of 2^tcb voxels per axis whose bit in gocc is clear hold no sample with alpha != 0
 // (cmap_cells_kernel); skipping them leaves either blend unchanged bit for bit.
+//
+// SHADE (VR_MODE_SCDVR; h is read by these instantiations only): dvr_march_kernel's SHADE -- the
+// headlight per ray, and per sample, once its colour C(v) is known, six more single samples of the
+// field (field_value_at) around the position of a sample in the volume with alpha != 0, the tap loop
+// rolled -- and from the central differences len2, mag = sqrtf(len2), the weight G(mag) that scales
+// the sample's alpha and, with len2 > 0 and a light, the normal that goes through shade_normal.  A
+// wave none of whose lanes lights the sample skips all of it.
+//
+// G(mag): j = the number of m_i <= mag, a sum of kMaxGopa compares against the wave-uniform m (the
+// unused ones NaN: never <= mag; a NaN mag: 0); the point max(j - 1, 0) as {m, inv, w, w of the next
+// point} in one 16-byte LDS read from the table at the head of LDS (kGopaLds bytes, ahead of the
+// carve-up above) that the workgroup's first lane stages from the kernel arguments; flat tails
+// (j == 0, j == n) give that point's w itself, otherwise the unfused lerp at
+// u = min((mag - m) * inv, 1) -- the law of the colour map with one channel.
+//
+// An alpha-0 sample is neither lit nor scaled: it stays the exact no-op of both blends that the
+// empty-cell skip (ESS, over CDVR's own cell bits) and the blank-batch skip rely on.  (No
+// amdgpu_waves_per_eu cap: profiles/scdvr/resource_usage.txt -- every instantiation fits without
+// scratch left to itself.)
 // ------------------------------------------------------------------------------------------------
 constexpr int kCmapK = 4;
 
-template <bool F2B, bool ESS, bool U8, bool SMALL, bool SEP>
-__global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame g, const WorkTile* __restrict__ work,
+template <bool F2B, bool ESS, bool U8, bool SMALL, bool SEP, bool SHADE>
+__global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame g, ScdvrFrame h,
+                                                         const WorkTile* __restrict__ work,
                                                          const void* __restrict__ vol,
                                                          const float2* __restrict__ gxi,
                                                          const float4* __restrict__ gcol,
                                                          const uint32_t* __restrict__ gocc,
                                                          float4* __restrict__ out) {
     constexpr int K = kCmapK;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // LDS: the points' colours | their (x, inv) | the cell bits (ESS) | the B table (SEP)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
+    // LDS: G's points (SHADE) | the points' colours | their (x, inv) | the cell bits (ESS) | the B
+    // table (SEP)
+    float4* s_G = reinterpret_cast<float4*>(smem_all);
+    unsigned char* smem = smem_all + (SHADE ? kGopaLds : 0);
     float4* s_col = reinterpret_cast<float4*>(smem);
     float2* s_xi = reinterpret_cast<float2*>(smem + (size_t)g.n * sizeof(float4));
     const bool occ_st = ESS && f.occ_lds;
@@ -76,6 +101,13 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
         s_col[threadIdx.x] = cv;
         s_xi[threadIdx.x] = xv;
     }
+    // G's table from the kernel arguments: constant indices only (a lane-indexed read of a by-value
+    // struct would go through scratch), so one lane stores the 16 entries
+    if (SHADE && threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < kMaxGopa; ++i)
+            s_G[i] = make_float4(h.m[i], h.inv[i], h.w[i], h.w[i + 1 < kMaxGopa ? i + 1 : i]);
+    }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int i = (int)threadIdx.x + u * kWgThreads;
@@ -103,11 +135,22 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
     auto position = [&](int s, float p[3]) { test_position<SEP>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
     int s_begin, s_end;
     float pa[3], dp[3], idp[3];
+    float L[3] = {0.0f, 0.0f, 0.0f};
+    bool lit = false;   // SHADE: the ray has a light direction
     {
         float pb[3];
         position(0, pa);
         position(f.S > 1 ? f.S - 1 : 0, pb);
         test_clip(f, pa, pb, dp, idp, s_begin, s_end);
+        if (SHADE) {   // headlight along the ray, in voxel space (dvr_march_kernel's, from the same two end points)
+            const float ex = pb[0] - pa[0], ey = pb[1] - pa[1], ez = pb[2] - pa[2];
+            const float n2 = (ex * ex + ey * ey) + ez * ez;
+            if (n2 > 0.0f) {
+                const float il = 1.0f / sqrtf(n2);
+                L[0] = -ex * il; L[1] = -ey * il; L[2] = -ez * il;
+                lit = true;
+            }
+        }
     }
 
     const float4 c0 = make_float4(g.c0[0], g.c0[1], g.c0[2], g.c0[3]);
@@ -246,8 +289,61 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
                 cs.y = flat ? ca.y : ca.y * u1 + cb.y * u;
                 cs.z = flat ? ca.z : ca.z * u1 + cb.z * u;
                 cs.w = flat ? ca.w : ca.w * u1 + cb.w * u;
-                const float4 cf = in[k] ? cs : c0;
+                float4 cf = in[k] ? cs : c0;
                 const int sk = F2B ? s + k : s - k;
+                // SHADE: the lit samples: in the volume (in[k] holds the range test too) with alpha != 0
+                const bool sh = SHADE && in[k] && cf.w != 0.0f;
+                if (SHADE && __any(sh)) {
+                    float ps[3];
+                    position(sk, ps);   // (the batch kept the sample's fractions only: the same position again)
+                    // gradient of the trilinear field at p: taps t = 2 a (q+) and 2 a + 1 (q-) of axis a, both
+                    // in the volume for a lane that lights (selects, no indexed arrays: the loop is rolled)
+                    float gx = 0.0f, gy = 0.0f, gz = 0.0f, vplus = 0.0f;
+#pragma unroll 1
+                    for (int t = 0; t < 6; ++t) {
+                        const int a = t >> 1;
+                        const float pc = a == 0 ? ps[0] : (a == 1 ? ps[1] : ps[2]);
+                        const float top = (float)(a == 0 ? xl : (a == 1 ? yl : zl));
+                        const float qp = fminf(pc + 1.0f, top), qm = fmaxf(pc - 1.0f, 0.0f);
+                        const float q = (t & 1) ? qm : qp;
+                        const float tv = field_value_at<U8>(sh, a == 0 ? q : ps[0], a == 1 ? q : ps[1],
+                                                            a == 2 ? q : ps[2], vrs, d3, d23, xl, yl, zl);
+                        if (t & 1) {
+                            const float span = qp - qm;
+                            const float ga = span > 0.0f ? (vplus - tv) / span : 0.0f;
+                            gx = a == 0 ? ga : gx;
+                            gy = a == 1 ? ga : gy;
+                            gz = a == 2 ? ga : gz;
+                        } else {
+                            vplus = tv;
+                        }
+                    }
+                    const float len2 = (gx * gx + gy * gy) + gz * gz;
+                    const float mag = sqrtf(len2);
+                    // gradient opacity G(mag), with or without a normal
+                    int jg = 0;   // the points m_i <= mag (a NaN: none)
+#pragma unroll
+                    for (int i = 0; i < kMaxGopa; ++i) jg += (int)(mag >= h.m[i]);
+                    const float4 ge = s_G[max(jg - 1, 0)];
+                    const float ug = fminf((mag - ge.x) * ge.y, 1.0f);
+                    const float ug1 = 1.0f - ug;
+                    const float gw = (jg == 0 || jg == h.n) ? ge.z : ge.z * ug1 + ge.w * ug;
+                    float4 nv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    if (lit && len2 > 0.0f) {   // (without a light direction: d = 1, spec = 0, as without a normal)
+                        const float inv = 1.0f / mag;
+                        nv = make_float4(-gx * inv, -gy * inv, -gz * inv, 1.0f);
+                        // two-sided: a normal facing away from the light is negated (exact), so the law's own
+                        // dot product is -ndl
+                        const float ndl = (nv.x * L[0] + nv.y * L[1]) + nv.z * L[2];
+                        if (ndl < 0.0f) { nv.x = -nv.x; nv.y = -nv.y; nv.z = -nv.z; }
+                    }
+                    float cr = cf.x, cg = cf.y, cb_ = cf.z;
+                    shade_normal(nv, L, h.ka, h.kd, h.ks, h.shininess, cr, cg, cb_);
+                    cf.x = sh ? cr : cf.x;
+                    cf.y = sh ? cg : cf.y;
+                    cf.z = sh ? cb_ : cf.z;
+                    cf.w = sh ? cf.w * gw : cf.w;
+                }
                 const float a = (F2B ? (sk < s_end) : (sk >= s_begin)) ? cf.w : 0.0f;
                 if (F2B) {
                     const float wt_ = T * a;
@@ -306,23 +402,27 @@ __global__ __launch_bounds__(256) void cmap_cells_kernel(const float2* __restric
 // Launch wrappers (called from vr_api.cpp)
 // ------------------------------------------------------------------------------------------------
 
-// LDS bytes of a CDVR workgroup (host: DVR's budget logic -- the B table is dropped, then the cell
-// bits, when the sum would pass kDvrLdsMax)
-size_t cmap_lds_bytes(const TestFrame& f, const CmapFrame& g, bool ess) {
-    return (size_t)g.n * sizeof(float4) + ((size_t)g.n * sizeof(float2) + 15) / 16 * 16 +
+// LDS bytes of a CDVR workgroup, or with shade an SCDVR one (host: DVR's budget logic -- the B table
+// is dropped, then the cell bits, when the sum would pass kDvrLdsMax)
+size_t cmap_lds_bytes(const TestFrame& f, const CmapFrame& g, bool ess, bool shade) {
+    return (shade ? (size_t)kGopaLds : 0) + (size_t)g.n * sizeof(float4) +
+           ((size_t)g.n * sizeof(float2) + 15) / 16 * 16 +
            (((ess && f.occ_lds) ? (size_t)f.occ_words * 4 : 0) + 15) / 16 * 16 +
            ((f.sep && f.sep_tab) ? (size_t)(f.S + 2 * kCmapK) * sizeof(float4) : 0);
 }
 
-hipError_t launch_cmap_march(const TestFrame& f, const CmapFrame& g, const WorkTile* work, int n_blocks, const void* vol,
-                             bool u8, const float2* xi, const float4* col, const uint32_t* occ, float4* out,
-                             hipStream_t st) {
+// shade: the coefficients and G of an SCDVR frame, or null for a CDVR frame (whose kernels read none)
+hipError_t launch_cmap_march(const TestFrame& f, const CmapFrame& g, const ScdvrFrame* shade, const WorkTile* work,
+                             int n_blocks, const void* vol, bool u8, const float2* xi, const float4* col,
+                             const uint32_t* occ, float4* out, hipStream_t st) {
     const bool f2b = (f.flags & 2) != 0, ess = (f.flags & 1) != 0 && f.zero_transparent && occ != nullptr;
     const bool small = g.n <= kCmapSmall, sep = f.sep != 0;
-    const size_t lds = cmap_lds_bytes(f, g, ess);
-#define VR_C5(F2B_, ESS_, U8_, SMALL_, SEP_)                                                                      \
-    hipLaunchKernelGGL((cmap_march_kernel<F2B_, ESS_, U8_, SMALL_, SEP_>), dim3(n_blocks), dim3(kWgThreads), lds, \
-                       st, f, g, work, vol, xi, col, occ, out)
+    const size_t lds = cmap_lds_bytes(f, g, ess, shade != nullptr);
+    const ScdvrFrame h = shade ? *shade : ScdvrFrame{};
+#define VR_C6(F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_)                                                                 \
+    hipLaunchKernelGGL((cmap_march_kernel<F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_>), dim3(n_blocks), dim3(kWgThreads), \
+                       lds, st, f, g, h, work, vol, xi, col, occ, out)
+#define VR_C5(F2B_, ESS_, U8_, SMALL_, SEP_) do { if (shade) VR_C6(F2B_, ESS_, U8_, SMALL_, SEP_, true); else VR_C6(F2B_, ESS_, U8_, SMALL_, SEP_, false); } while (0)
 #define VR_C4(F2B_, ESS_, U8_, SMALL_) do { if (sep) VR_C5(F2B_, ESS_, U8_, SMALL_, true); else VR_C5(F2B_, ESS_, U8_, SMALL_, false); } while (0)
 #define VR_C3(F2B_, ESS_, U8_) do { if (small) VR_C4(F2B_, ESS_, U8_, true); else VR_C4(F2B_, ESS_, U8_, false); } while (0)
 #define VR_C2(F2B_, ESS_) do { if (u8) VR_C3(F2B_, ESS_, true); else VR_C3(F2B_, ESS_, false); } while (0)
@@ -332,6 +432,7 @@ hipError_t launch_cmap_march(const TestFrame& f, const CmapFrame& g, const WorkT
 #undef VR_C3
 #undef VR_C4
 #undef VR_C5
+#undef VR_C6
     return hipGetLastError();
 }
 

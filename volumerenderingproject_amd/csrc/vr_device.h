@@ -217,8 +217,8 @@ struct IsoFrame {
     int32_t bound_bytes;        // bytes of the cells' upper bounds (one float per cell)
 };
 
-// The SDVR march (vr_sdvr.hip) takes DVR's TestFrame and DvrFrame unchanged and adds the Phong
-// coefficients, by value per launch like IsoFrame's:
+// The SDVR march (dvr_march_kernel's SHADE variants, vr_dvr.hip) takes DVR's TestFrame and DvrFrame
+// unchanged and adds the Phong coefficients, by value per launch like IsoFrame's:
 struct SdvrFrame {
     float ka, kd, ks, shininess;   // vr_params.shade_*
 };
@@ -235,8 +235,8 @@ struct CmapFrame {
     float x[kCmapSmall];        // n <= kCmapSmall: x[0 .. n), the rest NaN (no value is >= NaN)
 };
 
-// The SCDVR march (vr_scdvr.hip) takes CDVR's TestFrame, CmapFrame and device tables unchanged and adds,
-// by value per launch like IsoFrame's (so vr_set_gradient_opacity between queued frames needs no
+// The SCDVR march (cmap_march_kernel's SHADE variants, vr_cmap.hip) takes CDVR's TestFrame, CmapFrame and
+// device tables unchanged and adds, by value per launch like IsoFrame's (so vr_set_gradient_opacity between queued frames needs no
 // synchronisation): the Phong coefficients and the gradient-opacity map G (host/colormap.h).  The
 // march counts the m_i <= mag against the wave-uniform m and reads point max(j - 1, 0) from a
 // 16-entry LDS table {m_i, inv_i, w_i, w_{min(i + 1, n - 1)}} staged from these arguments.

@@ -1,6 +1,7 @@
 // vr_dvr.hip -- VR_MODE_DVR for gfx950: trilinear sample of the scalar field, then TransferFunction
 // classification (interpolate first, classify the interpolated value), and its setup kernels (the
-// byte copy of the volume, the min/max cells, the empty-cell bits).  Its own translation unit so it
+// byte copy of the volume, the min/max cells, the empty-cell bits); VR_MODE_SDVR is the same march with
+// every non-transparent in-volume sample lit (the kernel's SHADE flag).  Its own translation unit so it
 // compiles in parallel with vr_kernels.hip (VRC) and vr_test.hip (TEST).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,11 +41,23 @@ namespace vr {
 //
 // ESS: cells of 2^tcb voxels per axis whose bit in gocc is clear hold no sample with alpha > 0
 // (dvr_cells_kernel); skipping them leaves either blend unchanged bit for bit.
+//
+// SHADE (VR_MODE_SDVR; h is read by these instantiations only): per ray the headlight
+// L = -(p(S - 1) - p(0)) / |.|, from the two end points the clip evaluates anyway.  Per sample, once
+// its class is known: the lanes whose sample is in the volume with alpha != 0 run six more single
+// samples of the field (field_value_at) around the sample's position, turn the central differences
+// into a normal, face it to the light and put the segment's colour through shade_normal before the
+// blend.  The tap loop is rolled (selects, no indexed arrays) so the batch's live gather registers are
+// not multiplied by six, and a wave none of whose lanes shades the sample skips it.  An alpha-0 sample
+// is never shaded: it stays the exact no-op of both blends that the empty-cell skip (ESS) and the
+// blank-batch skip rely on, so the cell bits and their margin are DVR's.  (No amdgpu_waves_per_eu
+// cap: profiles/sdvr/resource_usage.txt -- every instantiation fits without scratch left to itself.)
 // ------------------------------------------------------------------------------------------------
 constexpr int kDvrK = 4;
 
-template <bool F2B, bool ESS, bool U8, bool SEG8, bool SEP>
-__global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g, const WorkTile* __restrict__ work,
+template <bool F2B, bool ESS, bool U8, bool SEG8, bool SEP, bool SHADE>
+__global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g, SdvrFrame h,
+                                                        const WorkTile* __restrict__ work,
                                                         const void* __restrict__ vol,
                                                         const float* __restrict__ gstart,
                                                         const float4* __restrict__ gseg,
@@ -119,11 +132,22 @@ __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g,
     auto position = [&](int s, float p[3]) { test_position<SEP>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
     int s_begin, s_end;
     float pa[3], dp[3], idp[3];
+    float L[3] = {0.0f, 0.0f, 0.0f};
+    bool lit = false;   // SHADE: the ray has a light direction
     {
         float pb[3];
         position(0, pa);
         position(f.S > 1 ? f.S - 1 : 0, pb);
         test_clip(f, pa, pb, dp, idp, s_begin, s_end);
+        if (SHADE) {   // headlight along the ray, in voxel space (iso_march_kernel's, from the same two end points)
+            const float ex = pb[0] - pa[0], ey = pb[1] - pa[1], ez = pb[2] - pa[2];
+            const float n2 = (ex * ex + ey * ey) + ez * ez;
+            if (n2 > 0.0f) {
+                const float il = 1.0f / sqrtf(n2);
+                L[0] = -ex * il; L[1] = -ey * il; L[2] = -ez * il;
+                lit = true;
+            }
+        }
     }
 
     const float4 tf0 = s_seg[g.seg0];
@@ -252,8 +276,51 @@ __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g,
                     }
                 }
                 const float4 cs = s_seg[seg];
-                const float4 cf = in[k] ? cs : tf0;
+                float4 cf = in[k] ? cs : tf0;
                 const int sk = F2B ? s + k : s - k;
+                // SHADE: the shaded samples: in the volume (in[k] holds the range test too) with alpha != 0
+                const bool sh = SHADE && in[k] && cf.w != 0.0f;
+                if (SHADE && __any(sh)) {
+                    float ps[3];
+                    position(sk, ps);   // (the batch kept the sample's fractions only: the same position again)
+                    // gradient of the trilinear field at p: taps t = 2 a (q+) and 2 a + 1 (q-) of axis a, both
+                    // in the volume for a lane that shades (selects, no indexed arrays: the loop is rolled)
+                    float gx = 0.0f, gy = 0.0f, gz = 0.0f, vplus = 0.0f;
+#pragma unroll 1
+                    for (int t = 0; t < 6; ++t) {
+                        const int a = t >> 1;
+                        const float pc = a == 0 ? ps[0] : (a == 1 ? ps[1] : ps[2]);
+                        const float top = (float)(a == 0 ? xl : (a == 1 ? yl : zl));
+                        const float qp = fminf(pc + 1.0f, top), qm = fmaxf(pc - 1.0f, 0.0f);
+                        const float q = (t & 1) ? qm : qp;
+                        const float tv = field_value_at<U8>(sh, a == 0 ? q : ps[0], a == 1 ? q : ps[1],
+                                                            a == 2 ? q : ps[2], vrs, d3, d23, xl, yl, zl);
+                        if (t & 1) {
+                            const float span = qp - qm;
+                            const float ga = span > 0.0f ? (vplus - tv) / span : 0.0f;
+                            gx = a == 0 ? ga : gx;
+                            gy = a == 1 ? ga : gy;
+                            gz = a == 2 ? ga : gz;
+                        } else {
+                            vplus = tv;
+                        }
+                    }
+                    const float len2 = (gx * gx + gy * gy) + gz * gz;
+                    float4 nv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    if (lit && len2 > 0.0f) {   // (without a light direction: d = 1, spec = 0, as without a normal)
+                        const float inv = 1.0f / sqrtf(len2);
+                        nv = make_float4(-gx * inv, -gy * inv, -gz * inv, 1.0f);
+                        // two-sided: a normal facing away from the light is negated (exact), so the law's own
+                        // dot product is -ndl
+                        const float ndl = (nv.x * L[0] + nv.y * L[1]) + nv.z * L[2];
+                        if (ndl < 0.0f) { nv.x = -nv.x; nv.y = -nv.y; nv.z = -nv.z; }
+                    }
+                    float cr = cf.x, cg = cf.y, cb = cf.z;
+                    shade_normal(nv, L, h.ka, h.kd, h.ks, h.shininess, cr, cg, cb);
+                    cf.x = sh ? cr : cf.x;
+                    cf.y = sh ? cg : cf.y;
+                    cf.z = sh ? cb : cf.z;
+                }
                 const float a = (F2B ? (sk < s_end) : (sk >= s_begin)) ? cf.w : 0.0f;
                 if (F2B) {
                     const float wt_ = T * a;
@@ -362,15 +429,18 @@ size_t dvr_lds_bytes(const TestFrame& f, const DvrFrame& g, bool ess) {
            ((f.sep && f.sep_tab) ? (size_t)(f.S + 2 * kDvrK) * sizeof(float4) : 0);
 }
 
-hipError_t launch_dvr_march(const TestFrame& f, const DvrFrame& g, const WorkTile* work, int n_blocks, const void* vol,
-                            bool u8, const float* start, const float4* seg, const uint32_t* occ, float4* out,
-                            hipStream_t st) {
+// shade: the coefficients of an SDVR frame, or null for a DVR frame (whose kernels read none)
+hipError_t launch_dvr_march(const TestFrame& f, const DvrFrame& g, const SdvrFrame* shade, const WorkTile* work,
+                            int n_blocks, const void* vol, bool u8, const float* start, const float4* seg,
+                            const uint32_t* occ, float4* out, hipStream_t st) {
     const bool f2b = (f.flags & 2) != 0, ess = (f.flags & 1) != 0 && f.zero_transparent && occ != nullptr;
     const bool seg8 = g.nseg <= 1 + kDvrSeg8, sep = f.sep != 0;
     const size_t lds = dvr_lds_bytes(f, g, ess);
-#define VR_D5(F2B_, ESS_, U8_, SEG8_, SEP_)                                                                     \
-    hipLaunchKernelGGL((dvr_march_kernel<F2B_, ESS_, U8_, SEG8_, SEP_>), dim3(n_blocks), dim3(kWgThreads), lds, \
-                       st, f, g, work, vol, start, seg, occ, out)
+    const SdvrFrame h = shade ? *shade : SdvrFrame{};
+#define VR_D6(F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_)                                                                \
+    hipLaunchKernelGGL((dvr_march_kernel<F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_>), dim3(n_blocks), dim3(kWgThreads), \
+                       lds, st, f, g, h, work, vol, start, seg, occ, out)
+#define VR_D5(F2B_, ESS_, U8_, SEG8_, SEP_) do { if (shade) VR_D6(F2B_, ESS_, U8_, SEG8_, SEP_, true); else VR_D6(F2B_, ESS_, U8_, SEG8_, SEP_, false); } while (0)
 #define VR_D4(F2B_, ESS_, U8_, SEG8_) do { if (sep) VR_D5(F2B_, ESS_, U8_, SEG8_, true); else VR_D5(F2B_, ESS_, U8_, SEG8_, false); } while (0)
 #define VR_D3(F2B_, ESS_, U8_) do { if (seg8) VR_D4(F2B_, ESS_, U8_, true); else VR_D4(F2B_, ESS_, U8_, false); } while (0)
 #define VR_D2(F2B_, ESS_) do { if (u8) VR_D3(F2B_, ESS_, true); else VR_D3(F2B_, ESS_, false); } while (0)
@@ -380,6 +450,7 @@ hipError_t launch_dvr_march(const TestFrame& f, const DvrFrame& g, const WorkTil
 #undef VR_D3
 #undef VR_D4
 #undef VR_D5
+#undef VR_D6
     return hipGetLastError();
 }
 

@@ -31,7 +31,7 @@ namespace vr {
 // After the loop the lanes with a hit run the tail together, once per ray: VR_ISO_REFINE bisection
 // rounds between samples s_h - 1 and s_h (when s_h - 1 is in the volume), six gradient taps at the
 // refined point and the Phong law.  Both loops are rolled around one single-sample helper
-// (iso_value_at), which keeps the kernel's size and registers near MIP's: 12 single samples per hit
+// (field_value_at, vr_march.h), which keeps the kernel's size and registers near MIP's: 12 single samples per hit
 // ray against the hundreds of the march.  Fractional sample coordinates take the per-sample
 // expressions of the position chain (test_B_entry under SEP; the LDS table holds integer samples only,
 // and equals those expressions bit for bit there).
@@ -64,60 +64,6 @@ __device__ __forceinline__ void iso_position(const TestFrame& f, const TestRay& 
 __device__ __forceinline__ bool iso_inside(const TestFrame& f, float px, float py, float pz) {
     return ((int)(__float_as_uint(px) < __float_as_uint(f.fd1)) & (int)(__float_as_uint(py) < __float_as_uint(f.fd2)) &
             (int)(__float_as_uint(pz) < __float_as_uint(f.fd3))) != 0;
-}
-
-// One sample of the field at a point inside the volume: corners (int)p and min((int)p + 1, d - 1),
-// weights p - (int)p, the gathers of the march (U8: four unaligned dwords of the byte copy; else eight
-// float gathers, a non-finite voxel reading as 0; the edge clamp by selects), lerp1 in y, x, z.  Lanes
-// with ok false issue no load and return 0.
-template <bool U8>
-__device__ __forceinline__ float iso_value_at(bool ok, float px, float py, float pz, __amdgpu_buffer_rsrc_t vrs, int d3,
-                                              int d23, int xl, int yl, int zl) {
-    const int ix = (int)px, iy = (int)py, iz = (int)pz;
-    const float dx = __builtin_amdgcn_fractf(px), dy = __builtin_amdgcn_fractf(py), dz = __builtin_amdgcn_fractf(pz);
-    const int base = ix * d23 + iy * d3 + iz;
-    const int ox = ix >= xl ? 0 : d23, oy = iy >= yl ? 0 : d3;
-    const bool lastz = iz >= zl;
-    int off[4];
-    off[0] = base;
-    off[1] = base + oy;
-    off[2] = base + ox;
-    off[3] = base + ox + oy;
-    uint32_t raw[U8 ? 4 : 8];
-#pragma unroll
-    for (int i = 0; i < (U8 ? 4 : 8); ++i) raw[i] = 0u;
-    if (ok) {
-        if (U8) {
-#pragma unroll
-            for (int xy = 0; xy < 4; ++xy) raw[xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy], 0, 0);
-        } else {
-            const int zs = lastz ? 0 : 4;
-#pragma unroll
-            for (int xy = 0; xy < 4; ++xy) {
-                raw[2 * xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy] * 4, 0, 0);
-                raw[2 * xy + 1] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy] * 4 + zs, 0, 0);
-            }
-        }
-    }
-    float c[8];   // corner kk = x << 2 | y << 1 | z
-#pragma unroll
-    for (int xy = 0; xy < 4; ++xy) {
-        if (U8) {
-            const uint32_t z0 = raw[xy] & 0xffu, z1 = (raw[xy] >> 8) & 0xffu;
-            c[2 * xy] = (float)z0;
-            c[2 * xy + 1] = (float)(lastz ? z0 : z1);
-        } else {
-#pragma unroll
-            for (int z = 0; z < 2; ++z) {   // a non-finite voxel reads as 0
-                const uint32_t u = raw[2 * xy + z];
-                c[2 * xy + z] = (u & 0x7f800000u) == 0x7f800000u ? 0.0f : __uint_as_float(u);
-            }
-        }
-    }
-    const float y1 = lerp1(c[0], c[2], dy), y2 = lerp1(c[1], c[3], dy);
-    const float y3 = lerp1(c[4], c[6], dy), y4 = lerp1(c[5], c[7], dy);
-    const float z1 = lerp1(y1, y3, dx), z2 = lerp1(y2, y4, dx);
-    return lerp1(z1, z2, dz);
 }
 
 // (ESS, U8, SEP -- the flagship path -- allocates 80 VGPRs left to itself, 6 waves per SIMD where MIP's
@@ -281,7 +227,7 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
             float pm[3];
             iso_position<SEP>(f, ray, mid, pm);
             const bool ok = iso_inside(f, pm[0], pm[1], pm[2]);
-            const float v = iso_value_at<U8>(ok, pm[0], pm[1], pm[2], vrs, d3, d23, xl, yl, zl);
+            const float v = field_value_at<U8>(ok, pm[0], pm[1], pm[2], vrs, d3, d23, xl, yl, zl);
             const bool take = ok && v >= iso;
             hi = (refinable && take) ? mid : hi;
             lo = (refinable && !take) ? mid : lo;
@@ -299,7 +245,7 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
             const float top = (float)(a == 0 ? xl : (a == 1 ? yl : zl));
             const float qp = fminf(pc + 1.0f, top), qm = fmaxf(pc - 1.0f, 0.0f);
             const float q = (t & 1) ? qm : qp;
-            const float v = iso_value_at<U8>(true, a == 0 ? q : ps[0], a == 1 ? q : ps[1], a == 2 ? q : ps[2], vrs, d3,
+            const float v = field_value_at<U8>(true, a == 0 ? q : ps[0], a == 1 ? q : ps[1], a == 2 ? q : ps[2], vrs, d3,
                                              d23, xl, yl, zl);
             if (t & 1) {
                 const float span = qp - qm;

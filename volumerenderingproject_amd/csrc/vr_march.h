@@ -1,5 +1,6 @@
 // vr_march.h -- device helpers shared by the march kernels (vr_kernels.hip: VRC and the setup
-// kernels; vr_test.hip: TEST; vr_dvr.hip: DVR; vr_mip.hip: MIP; vr_iso.hip: ISO).  Internal, not the ABI.
+// kernels; vr_test.hip: TEST; vr_dvr.hip: DVR and SDVR; vr_cmap.hip: CDVR and SCDVR; vr_mip.hip: MIP;
+// vr_iso.hip: ISO).  Internal, not the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -272,6 +273,61 @@ __device__ __forceinline__ float lerp1(float a, float b, float w) {
 #pragma clang fp contract(off)
     const float u = 1.0f - w;
     return a * u + b * w;
+}
+
+// One sample of the field at a point inside the volume (ISO's bisection and gradient taps, the gradient
+// taps of the DVR and CDVR marches' SHADE variants): corners (int)p and min((int)p + 1, d - 1), weights
+// p - (int)p, the gathers of the march (U8: four unaligned dwords of the byte copy; else eight float
+// gathers, a non-finite voxel reading as 0; the edge clamp by selects), lerp1 in y, x, z.  Lanes with
+// ok false issue no load and return 0.
+template <bool U8>
+__device__ __forceinline__ float field_value_at(bool ok, float px, float py, float pz, __amdgpu_buffer_rsrc_t vrs,
+                                                int d3, int d23, int xl, int yl, int zl) {
+    const int ix = (int)px, iy = (int)py, iz = (int)pz;
+    const float dx = __builtin_amdgcn_fractf(px), dy = __builtin_amdgcn_fractf(py), dz = __builtin_amdgcn_fractf(pz);
+    const int base = ix * d23 + iy * d3 + iz;
+    const int ox = ix >= xl ? 0 : d23, oy = iy >= yl ? 0 : d3;
+    const bool lastz = iz >= zl;
+    int off[4];
+    off[0] = base;
+    off[1] = base + oy;
+    off[2] = base + ox;
+    off[3] = base + ox + oy;
+    uint32_t raw[U8 ? 4 : 8];
+#pragma unroll
+    for (int i = 0; i < (U8 ? 4 : 8); ++i) raw[i] = 0u;
+    if (ok) {
+        if (U8) {
+#pragma unroll
+            for (int xy = 0; xy < 4; ++xy) raw[xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy], 0, 0);
+        } else {
+            const int zs = lastz ? 0 : 4;
+#pragma unroll
+            for (int xy = 0; xy < 4; ++xy) {
+                raw[2 * xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy] * 4, 0, 0);
+                raw[2 * xy + 1] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy] * 4 + zs, 0, 0);
+            }
+        }
+    }
+    float c[8];   // corner kk = x << 2 | y << 1 | z
+#pragma unroll
+    for (int xy = 0; xy < 4; ++xy) {
+        if (U8) {
+            const uint32_t z0 = raw[xy] & 0xffu, z1 = (raw[xy] >> 8) & 0xffu;
+            c[2 * xy] = (float)z0;
+            c[2 * xy + 1] = (float)(lastz ? z0 : z1);
+        } else {
+#pragma unroll
+            for (int z = 0; z < 2; ++z) {   // a non-finite voxel reads as 0
+                const uint32_t u = raw[2 * xy + z];
+                c[2 * xy + z] = (u & 0x7f800000u) == 0x7f800000u ? 0.0f : __uint_as_float(u);
+            }
+        }
+    }
+    const float y1 = lerp1(c[0], c[2], dy), y2 = lerp1(c[1], c[3], dy);
+    const float y3 = lerp1(c[4], c[6], dy), y4 = lerp1(c[5], c[7], dy);
+    const float z1 = lerp1(y1, y3, dx), z2 = lerp1(y2, y4, dx);
+    return lerp1(z1, z2, dz);
 }
 
 // Headlight Phong at a sample (oracle or_shade: same operations, same order):
