@@ -19,6 +19,7 @@ ONE = [(0.0, 1.0, (0.5, 0.6, 0.7, 0.1))]                                        
 BLOCK_TF = [(0.0, 0.05, (0.0, 0.0, 0.0, 0.0)), (0.05, 1.0, (1.0, 0.5, 0.25, 0.5))]
 
 _VOLUMES = {}
+BLOB_CALS = {"blob200": 200.7, "blob1000": 1000.25}   # test_gpu_params.test_cal_max_not_an_integer's values
 
 
 def block01():
@@ -49,6 +50,10 @@ def volume(name):
             _VOLUMES[name] = (pc.cube(), 255.0)
         elif name == "blob":
             _VOLUMES[name] = (pc.blob(), 255.0)
+        elif name in BLOB_CALS:    # the blob at a fractional cal_max (tests/field_param_cases.py)
+            _VOLUMES[name] = (pc.blob(), BLOB_CALS[name])
+        elif name in pc.DEEP:      # the needles of param_cases.DEEP
+            _VOLUMES[name] = (pc.tiny_volume(pc.DEEP[name]), 255.0)
         elif name == "special":
             _VOLUMES[name] = (pc.blob_special(), 255.0)
         elif name == "small":

@@ -4,7 +4,8 @@ every compositing mode.  Exact and ESS-only frames are bitwise the oracle's (the
 back-to-front blend, kernel.cu:194-225); ESS + ERT and ERT alone within 1e-4; TEST exact bitwise
 (kernel.cu:72-187).  Covers the general-view paths (padded leaf maps, lazy empty-space tests,
 empty-cell skipping of exact frames) on views no other test picks.  The same views in DVR, MIP and ISO
-against tests/dvr_ref.py, mip_ref.py and iso_ref.py (test_random_views_field_modes)."""
+against tests/dvr_ref.py, mip_ref.py and iso_ref.py (test_random_views_field_modes), and in SDVR, CDVR and
+SCDVR against tests/sdvr_ref.py, cmap_ref.py and scdvr_ref.py (test_random_views_lit_field_modes)."""
 import math
 
 import numpy as np
@@ -109,3 +110,49 @@ def test_random_views_field_modes(avg152, oracle_mod, seed):
                         assert_same(r.render(params(ISO, W, H, S, flags), cam), iref, (i, "iso", iso, flags))
     # the views bite (iso_ref's records over both isovalues: 21223 hit rays and 6403 refinable ones at the least)
     assert hits >= 2000 and refinable >= 1500, (seed, hits, refinable)
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_random_views_lit_field_modes(seed):
+    """The same views in the three modes added after ISO, against their numpy restatements
+    (tests/field_param_cases.py builds them): SDVR under the default TF with (0.2, 0.5, 0.4, 0), CDVR under
+    cmap_cases.SMOOTH5, SCDVR under SMOOTH5 with scdvr_cases.EDGES and the same coefficients.  Exact and ESS
+    frames are bitwise the restatement's, on the byte-copy context for every view and on the float-volume one
+    (dvr_volume = 1) for every third.
+
+    ERT and ESS | ERT against the exact frame: S reaches 319 here, and the project's bound 1e-5 R + 6 S 2^-24 M
+    (test_gpu_params.test_ert_epsilon; R = M = 1.1, the largest lit colour c * 0.7 + 0.4) passes 1e-4 for S
+    above about 250, so each view is held to the larger of the two (field_param_cases.random_ert_bound).
+    Largest error seen on the MI355X: 8.3e-6, 8.2e-6 and 8.2e-6 for seeds 1, 2 and 3 (264 frames each),
+    against bounds of 1e-4 to 1.37e-4; it is printed."""
+    import cmap_cases as cc
+    import field_param_cases as fp
+    import scdvr_cases as xc
+    import sdvr_cases as sc
+    from test_gpu_dvr import assert_bits
+    vol, cal = sc.volume("avg152")
+    worst = frames = 0
+    with vr.VolumeRenderer(vol, cal, device=0) as a, \
+            vr.VolumeRenderer(vol, cal, device=0, options=vr.default_options(dvr_volume=1)) as b:
+        for r in (a, b):
+            r.set_colormap(cc.map_of(fp.SCDVR_SETS[0][0], cal))
+            r.set_gradient_opacity(xc.gopa_of(fp.SCDVR_SETS[0][1]))
+        for i, view in enumerate(fp.random_view_cases(seed)):
+            refs = fp.random_references(view)[0]
+            bound = fp.random_ert_bound(view.S)
+            cam = view.gpu_camera()
+            cases = {fp.SDVR: fp.sdvr_case(view, 0, "avg152"), fp.CDVR: fp.cdvr_case(view, "avg152"),
+                     fp.SCDVR: fp.scdvr_case(view, 0, "avg152")}
+            for r in ((a, b) if i % 3 == 0 else (a,)):
+                for mode, case in cases.items():
+                    exact = r.render(case.gpu_params(0, mode=mode), cam)
+                    assert_bits(exact, refs[mode], (seed, i, mode, "exact"))
+                    assert_bits(r.render(case.gpu_params(E, mode=mode), cam), exact, (seed, i, mode, "ess"))
+                    for flags in (T, E | T):
+                        got = r.render(case.gpu_params(flags, mode=mode), cam)
+                        err = float(np.abs(got - exact).max())
+                        worst = max(worst, err)
+                        assert err <= bound, (seed, i, mode, flags, view.S, err, bound)
+                        assert np.all(got[..., 3] == 1.0)
+                    frames += 4
+    print("random views, lit field modes: seed", seed, "frames compared", frames, "largest ERT error", worst)
