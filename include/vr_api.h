@@ -531,6 +531,43 @@ int vr_get_gradient_opacity(vr_ctx* ctx, vr_gopa_point* out, int32_t capacity, i
  * what the march scales alpha with.  The same checks as vr_set_gradient_opacity (and count >= 0). */
 int vr_gradient_opacity_eval(const vr_gopa_point* points, int32_t n, const float* mag, int64_t count, float* w_out);
 
+/* The crop box: a region of interest for the six modes that march the trilinear field (VR_MODE_DVR,
+ * MIP, ISO, SDVR, CDVR, SCDVR), in voxel coordinates -- the unit of p, vr_set_isosurface and
+ * vr_set_colormap.  vr_set_crop_box(ctx, NULL, NULL) turns it off; a context starts with it off.
+ * VR_EINVAL for a null context, exactly one null pointer, a non-finite component, or lo[a] > hi[a];
+ * lo[a] == hi[a] is allowed (an empty box) and the box may reach beyond the volume.
+ * vr_get_crop_box (VR_EINVAL for a null argument) returns the last box set (zeros before the first)
+ * and whether it is on.
+ *
+ * Rule.  A sample at position p is in the box iff lo[a] <= p_a && p_a < hi[a] on every axis: float32
+ * compares of the sample's own position against the stored floats, no arithmetic.  With the box on,
+ * "in the volume" in a field mode's definition reads "in the volume and in the box" at every place it
+ * occurs, and nothing else changes:
+ *   DVR, CDVR    a sample not in the box has the colour of a sample outside the volume
+ *                (TF((float)(0.0f / cal_max)), or C(0.0f)).
+ *   SDVR, SCDVR  the same, and such a sample is neither lit nor modulated: the lit samples are those in
+ *                the volume and in the box with a != 0.
+ *   MIP          the maximum runs over the in-box samples; a ray without one is the background.
+ *   ISO          all three uses of the in-volume test also test the box: the hit test (step 2), the
+ *                "sample s_h - 1 is in the volume" condition of step 3, and the test on every
+ *                bisection midpoint.  The cut face sits at the first in-box sample, as the volume's
+ *                faces do.
+ * The field itself never changes: corners, edge clamps (min((int)p + 1, d - 1)), the six gradient taps
+ * (q+ = min(p_a + 1, d_a - 1) and so on) and the headlight L (from p(0) and p(S - 1)) read the whole
+ * volume, so a cut face is shaded by the data's true gradient.  VR_FLAG_ESS stays bitwise the exact
+ * frame in every mode, MIP's and ISO's four flag combinations stay bitwise equal, VR_FLAG_ERT is as in
+ * each mode, and "zero transparent" keeps each mode's meaning (without it the samples outside the box
+ * are TF(0) fog, every one of them blended).  VR_MODE_VRC and VR_MODE_TEST ignore the box.  With the box
+ * off, or a box that contains [0, d) on every axis, every frame is bitwise the frame without one.
+ *
+ * Host state only, like vr_set_isosurface: the box travels to the march by value with each launch and
+ * the culls (the visible rectangle, the hull, vr_visible_tiles, the multi-GPU tile deal) project it in
+ * the dataset box's place, so a call between queued asynchronous frames needs no synchronisation and
+ * rebuilds nothing; each frame shows the box current when it was enqueued.  Multi-GPU semantics are
+ * vr_set_isosurface's. */
+int vr_set_crop_box(vr_ctx* ctx, const float lo[3], const float hi[3]);   /* NULL, NULL: off */
+int vr_get_crop_box(vr_ctx* ctx, float lo[3], float hi[3], int32_t* enabled);
+
 /* deallocateDeviceMemory (kernel.cu:1072-1093). */
 int vr_destroy(vr_ctx* ctx);
 

@@ -169,6 +169,11 @@ public:
     void set_isosurface(float iso_value, const float (&rgb)[3]) {
         check(vr_set_isosurface(ctx_, iso_value, rgb), "vr_set_isosurface");
     }
+    // the six field modes: the crop box lo <= p < hi in voxel coordinates; clear_crop_box turns it off
+    void set_crop_box(const float (&lo)[3], const float (&hi)[3]) {
+        check(vr_set_crop_box(ctx_, lo, hi), "vr_set_crop_box");
+    }
+    void clear_crop_box() { check(vr_set_crop_box(ctx_, nullptr, nullptr), "vr_set_crop_box"); }
     // VR_MODE_CDVR: the piecewise-linear RGBA colour map, x in voxel units and strictly ascending
     void set_colormap(const std::vector<vr_cmap_point>& points) {
         check(vr_set_colormap(ctx_, points.data(), (int32_t)points.size()), "vr_set_colormap");

@@ -229,6 +229,11 @@ struct vr_ctx {
     // mip_bound
     float iso_value = 0.0f;
     float iso_rgb[3] = {1.0f, 1.0f, 1.0f};
+    // The crop box of the six field modes (vr_set_crop_box), voxel coordinates as the caller gave them;
+    // host state only -- the marches get the effective box by value per launch (vr::CropBox), and the
+    // culls project it in the dataset box's place (project_box_test)
+    bool crop_on = false;
+    float crop_lo[3] = {0.0f, 0.0f, 0.0f}, crop_hi[3] = {0.0f, 0.0f, 0.0f};
     // VR_MODE_CDVR (vr_cmap.hip): the colour map as the caller gave it and as the law reads it
     // (host/colormap.h; create: the grey ramp 0 .. cal_max), C(0.0f) and its transparency -- host
     // state, set by vr_set_colormap -- and, rebuilt by the next CDVR frame after a change

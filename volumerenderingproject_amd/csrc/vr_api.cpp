@@ -69,18 +69,18 @@ hipError_t launch_test_march(const TestFrame&, const WorkTile*, const int32_t*, 
 hipError_t launch_test_occupancy(const uint8_t*, int64_t, int64_t, int64_t, int, int, int, int, const uint8_t*,
                                  unsigned long long*, hipStream_t);
 hipError_t launch_dvr_march(const TestFrame&, const DvrFrame&, const SdvrFrame*, const WorkTile*, int, const void*, bool,
-                            const float*, const float4*, const uint32_t*, float4*, hipStream_t);
+                            const float*, const float4*, const uint32_t*, float4*, hipStream_t, const CropBox*);
 size_t dvr_lds_bytes(const TestFrame&, const DvrFrame&, bool);
 hipError_t launch_dvr_bytes(const float*, int64_t, uint8_t*, int32_t*, hipStream_t);
 hipError_t launch_dvr_minmax(const float*, int64_t, int64_t, int64_t, int, int, int, int, float2*, hipStream_t);
 hipError_t launch_dvr_cells(const float2*, int64_t, const float*, const float4*, int, unsigned long long*, hipStream_t);
 hipError_t launch_mip_march(const TestFrame&, const MipFrame&, const WorkTile*, int, const void*, bool, const float*,
-                            float4*, hipStream_t);
+                            float4*, hipStream_t, const CropBox*);
 hipError_t launch_mip_bounds(const float2*, int64_t, float*, hipStream_t);
 hipError_t launch_iso_march(const TestFrame&, const IsoFrame&, const WorkTile*, int, const void*, bool, const float*,
-                            float4*, hipStream_t);
+                            float4*, hipStream_t, const CropBox*);
 hipError_t launch_cmap_march(const TestFrame&, const CmapFrame&, const ScdvrFrame*, const WorkTile*, int, const void*, bool,
-                             const float2*, const float4*, const uint32_t*, float4*, hipStream_t);
+                             const float2*, const float4*, const uint32_t*, float4*, hipStream_t, const CropBox*);
 size_t cmap_lds_bytes(const TestFrame&, const CmapFrame&, bool, bool);
 hipError_t launch_cmap_cells(const float2*, int64_t, const float2*, const float4*, int, unsigned long long*, hipStream_t);
 static_assert(kMaxGopa == VR_GOPA_MAX_POINTS, "vr_device.h and vr_api.h disagree on the gradient-opacity map's size");
@@ -144,6 +144,31 @@ bool mode_cmap(const vr_params* p) { return p->mode == VR_MODE_CDVR || p->mode =
 // "TF(0) is transparent" as a frame of this mode reads it: VR_MODE_CDVR's and VR_MODE_SCDVR's is C(0.0f).a == 0
 bool mode_zero_transparent(const vr_ctx* c, const vr_params* p) {
     return mode_cmap(p) ? c->cmap_zero_transparent : c->zero_transparent;
+}
+
+// The modes that march the trilinear field, the ones vr_set_crop_box applies to
+bool mode_field(const vr_params* p) {
+    return p->mode == VR_MODE_DVR || p->mode == VR_MODE_SDVR || p->mode == VR_MODE_MIP || p->mode == VR_MODE_ISO ||
+           mode_cmap(p);
+}
+
+// The effective crop box of a frame of this mode, E = [max(lo, 0), min(hi, d)) per axis: a position is
+// in the volume and in the box iff it is in E (the conjunction of two interval tests is the test
+// against their intersection; max and min of floats are exact, (float)d the marches' own fd).  False with
+// the box off or a mode that ignores it.  An E empty on some axis (*empty) becomes lo = hi = +0 on all
+// three, which no position satisfies (vr_device.h CropBox).
+bool crop_box_of(const vr_ctx* c, const vr_params* p, CropBox* cb, bool* empty = nullptr) {
+    if (!c->crop_on || !mode_field(p)) return false;
+    bool none = false;
+    for (int a = 0; a < 3; ++a) {
+        cb->lo[a] = std::max(c->crop_lo[a], 0.0f);   // (a -0 lower bound reads as +0: the same compares)
+        cb->hi[a] = std::min(c->crop_hi[a], (float)c->d[a]);
+        none = none || !(cb->lo[a] < cb->hi[a]);
+    }
+    if (none)
+        for (int a = 0; a < 3; ++a) cb->lo[a] = cb->hi[a] = 0.0f;
+    if (empty) *empty = none;
+    return true;
 }
 
 // VR_MODE_SCDVR's gradient-opacity map as host state (validated: gopa_build).  Nothing on the device
@@ -960,6 +985,18 @@ int project_box(const vr_ctx* c, const vr_params* p, const vr_camera* cam, doubl
 int project_box_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam, double xy[8][2]) {
     // (CDVR, SCDVR: a sample outside the volume is C(0.0f), the colour map's own zero transparency)
     if (!mode_zero_transparent(c, p) && p->mode != VR_MODE_MIP && p->mode != VR_MODE_ISO) return 2;
+    // field modes under a crop box: a sample outside the effective box E is TF(0) (DVR ...) or takes no
+    // part (MIP, ISO) like one outside the volume, so E's corners are mapped in the dataset box's place
+    // and an empty E leaves nothing visible
+    double blo[3] = {0.0, 0.0, 0.0}, bhi[3] = {(double)c->d[0], (double)c->d[1], (double)c->d[2]};
+    {
+        CropBox cb;
+        bool empty = false;
+        if (crop_box_of(c, p, &cb, &empty)) {
+            if (empty) return 0;
+            for (int a = 0; a < 3; ++a) { blo[a] = cb.lo[a]; bhi[a] = cb.hi[a]; }
+        }
+    }
     CameraState cs;
     cs.pos = {cam->pos[0], cam->pos[1], cam->pos[2]};
     cs.up = {cam->up[0], cam->up[1], cam->up[2]};
@@ -995,7 +1032,7 @@ int project_box_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam, 
     const double t[3] = {M[12], M[13], M[14]};
     for (int k = 0; k < 8; ++k) {
         double v[3];
-        for (int a = 0; a < 3; ++a) v[a] = (((k >> a) & 1) ? (double)c->d[a] : 0.0) - t[a];
+        for (int a = 0; a < 3; ++a) v[a] = (((k >> a) & 1) ? bhi[a] : blo[a]) - t[a];
         for (int r = 0; r < 2; ++r) xy[k][r] = Li[r][0] * v[0] + Li[r][1] * v[1] + Li[r][2] * v[2];
         if (!std::isfinite(xy[k][0]) || !std::isfinite(xy[k][1])) return 2;
     }
@@ -1109,6 +1146,13 @@ std::vector<int32_t> visible_tiles(const vr_ctx* c, const vr_params* p, const vr
     std::memcpy(key.data(), p, sizeof(vr_params));
     std::memcpy(key.data() + sizeof(vr_params) / 4, cam, sizeof(vr_camera));
     key[key.size() - 3] = (uint32_t)tw; key[key.size() - 2] = (uint32_t)th; key[key.size() - 1] = (uint32_t)c->cull;
+    {   // the crop box the frame's culls project (a frame that ignores it keeps the box-off key)
+        CropBox cb;
+        if (crop_box_of(c, p, &cb)) {
+            key.resize(key.size() + 6);
+            std::memcpy(key.data() + key.size() - 6, &cb, sizeof cb);
+        }
+    }
     auto it = c->vis_cache.find(key);
     if (it != c->vis_cache.end()) return it->second;
     std::vector<int32_t> v = visible_tiles_uncached(c, p, cam, tw, th);
@@ -1948,6 +1992,10 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             f.bg_group = kBgGroup;
             n_launch = wc->bg_first + (wc->n_work - wc->bg_first + kBgGroup - 1) / kBgGroup;
         }
+        // the crop box current now, by value with the launch (vr_set_crop_box between queued frames touches
+        // no device state); null: off, or a mode that ignores it -- the CROP = false instantiations
+        CropBox crop_box;
+        const CropBox* crop = crop_box_of(c, p, &crop_box) ? &crop_box : nullptr;
         if (dvr) {
             // the DVR march, or SDVR's (its SHADE variant): TEST's frame with its own cells, plus the TF's
             // segments (ensure_dvr)
@@ -1959,7 +2007,7 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             SdvrFrame h;   // SDVR: the Phong coefficients by value per frame, like ISO's
             set_phong(h, p);
             hip_check(launch_dvr_march(f, g, sdvr ? &h : nullptr, wc->work, n_launch, v.p, v.u8, c->dvr_start.as<float>(),
-                                       c->dvr_seg.as<float4>(), c->dvr_occ.as<uint32_t>(), out, c->stream));
+                                       c->dvr_seg.as<float4>(), c->dvr_occ.as<uint32_t>(), out, c->stream, crop));
         } else if (cdvr) {
             // the CDVR march, or SCDVR's (its SHADE variant): TEST's frame with DVR's cells under the colour
             // map's own bits, plus the map's tables (ensure_cmap)
@@ -1975,7 +2023,7 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
                 h.m[i] = c->gopa.m[i]; h.inv[i] = c->gopa.inv[i]; h.w[i] = c->gopa.w[i];
             }
             hip_check(launch_cmap_march(f, g, scdvr ? &h : nullptr, wc->work, n_launch, v.p, v.u8, c->cmap_xi.as<float2>(),
-                                        c->cmap_col.as<float4>(), c->cmap_occ.as<uint32_t>(), out, c->stream));
+                                        c->cmap_col.as<float4>(), c->cmap_occ.as<uint32_t>(), out, c->stream, crop));
         } else if (mip) {
             // the MIP march: TEST's frame with DVR's cells, plus the cells' bounds (ensure_mip)
             const FieldVolume v = field_frame(c, f);
@@ -1985,7 +2033,8 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             g.vol_bound = c->mip_vol_bound;
             g.vol_bytes = v.bytes;
             g.bound_bytes = (int32_t)((int64_t)f.tnc[0] * f.tnc[1] * f.tnc[2] * 4);   // (<= 2^18 cells)
-            hip_check(launch_mip_march(f, g, wc->work, n_launch, v.p, v.u8, c->mip_bound.as<float>(), out, c->stream));
+            hip_check(launch_mip_march(f, g, wc->work, n_launch, v.p, v.u8, c->mip_bound.as<float>(), out, c->stream,
+                                       crop));
         } else if (iso) {
             // the ISO march: MIP's frame and bounds, plus the isovalue, the colour and the Phong
             // coefficients by value (vr_set_isosurface between queued frames touches no device state)
@@ -1997,7 +2046,8 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             set_phong(g, p);
             g.vol_bytes = v.bytes;
             g.bound_bytes = (int32_t)((int64_t)f.tnc[0] * f.tnc[1] * f.tnc[2] * 4);   // (<= 2^18 cells)
-            hip_check(launch_iso_march(f, g, wc->work, n_launch, v.p, v.u8, c->mip_bound.as<float>(), out, c->stream));
+            hip_check(launch_iso_march(f, g, wc->work, n_launch, v.p, v.u8, c->mip_bound.as<float>(), out, c->stream,
+                                       crop));
         } else {
         // axis views: the march axis's tables built here once per view and staged by every workgroup
         // (per stream, like the VRC view tables; a new view first drains the launches of this stream)
@@ -2353,6 +2403,35 @@ int vr_get_isosurface(vr_ctx* c, float* iso_value, float rgb[3]) {
     if (!c || !iso_value || !rgb) return VR_EINVAL;
     *iso_value = c->iso_value;
     for (int a = 0; a < 3; ++a) rgb[a] = c->iso_rgb[a];
+    return VR_OK;
+}
+
+// The crop box of the six field modes (voxel coordinates; NULL, NULL: off): host state only, passed to
+// the marches by value per launch (CropBox) like vr_set_isosurface's values and projected by the culls
+// of the frames enqueued from now on, so nothing is rebuilt and queued frames keep the box they were
+// launched with.
+int vr_set_crop_box(vr_ctx* c, const float lo[3], const float hi[3]) {
+    if (!c || (lo == nullptr) != (hi == nullptr)) return VR_EINVAL;
+    struct A { bool on; float lo[3], hi[3]; } a{lo != nullptr, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
+    for (int i = 0; lo && i < 3; ++i) {
+        if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || lo[i] > hi[i]) return VR_EINVAL;
+        a.lo[i] = lo[i];
+        a.hi[i] = hi[i];
+    }
+    return guard([&] {
+        group_for_each(c, [](vr_ctx* pc, void* p) {
+            const A* x = static_cast<const A*>(p);
+            pc->crop_on = x->on;
+            for (int i = 0; i < 3; ++i) { pc->crop_lo[i] = x->lo[i]; pc->crop_hi[i] = x->hi[i]; }
+        }, &a);
+        return VR_OK;
+    });
+}
+
+int vr_get_crop_box(vr_ctx* c, float lo[3], float hi[3], int32_t* enabled) {
+    if (!c || !lo || !hi || !enabled) return VR_EINVAL;
+    *enabled = c->crop_on ? 1 : 0;
+    for (int a = 0; a < 3; ++a) { lo[a] = c->crop_lo[a]; hi[a] = c->crop_hi[a]; }
     return VR_OK;
 }
 

@@ -55,17 +55,21 @@ namespace vr {
 // empty-cell skip (ESS, over CDVR's own cell bits) and the blank-batch skip rely on.  (No
 // amdgpu_waves_per_eu cap: profiles/scdvr/resource_usage.txt -- every instantiation fits without
 // scratch left to itself.)
+//
+// CROP (vr_set_crop_box; bx is read by these instantiations only): dvr_march_kernel's CROP -- the
+// effective box in the volume's place in in[k] and in the ESS first-sample test, crop_clip for the ray
+// range; a sample not in the box is C(0.0f), neither lit nor scaled.
 // ------------------------------------------------------------------------------------------------
 constexpr int kCmapK = 4;
 
-template <bool F2B, bool ESS, bool U8, bool SMALL, bool SEP, bool SHADE>
+template <bool F2B, bool ESS, bool U8, bool SMALL, bool SEP, bool SHADE, bool CROP>
 __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame g, ScdvrFrame h,
                                                          const WorkTile* __restrict__ work,
                                                          const void* __restrict__ vol,
                                                          const float2* __restrict__ gxi,
                                                          const float4* __restrict__ gcol,
                                                          const uint32_t* __restrict__ gocc,
-                                                         float4* __restrict__ out) {
+                                                         float4* __restrict__ out, CropBox bx) {
     constexpr int K = kCmapK;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
     // LDS: G's points (SHADE) | the points' colours | their (x, inv) | the cell bits (ESS) | the B
@@ -141,7 +145,8 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
         float pb[3];
         position(0, pa);
         position(f.S > 1 ? f.S - 1 : 0, pb);
-        test_clip(f, pa, pb, dp, idp, s_begin, s_end);
+        if (CROP) crop_clip(f, bx, pa, pb, dp, idp, s_begin, s_end);
+        else test_clip(f, pa, pb, dp, idp, s_begin, s_end);
         if (SHADE) {   // headlight along the ray, in voxel space (dvr_march_kernel's, from the same two end points)
             const float ex = pb[0] - pa[0], ey = pb[1] - pa[1], ez = pb[2] - pa[2];
             const float n2 = (ex * ex + ey * ey) + ez * ez;
@@ -171,9 +176,11 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
             float* p = pfirst;
             position(s, p);
             // (bitwise, not short-circuit: && chains compile to exec-mask branches)
-            const bool inside = ((int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
-                                 (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
-                                 (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            bool inside = ((int)(__float_as_uint(p[0]) < __float_as_uint(CROP ? bx.hi[0] : f.fd1)) &
+                           (int)(__float_as_uint(p[1]) < __float_as_uint(CROP ? bx.hi[1] : f.fd2)) &
+                           (int)(__float_as_uint(p[2]) < __float_as_uint(CROP ? bx.hi[2] : f.fd3))) != 0;
+            // CROP: the effective box's upper bounds stand in fd's place; its lower compares (vr_march.h)
+            if (CROP) inside = ((int)inside & (int)crop_lower<CROP>(bx, p[0], p[1], p[2])) != 0;
             int cc[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) cc[c] = inside ? ((int)p[c] >> f.tcb) : 0;
@@ -198,9 +205,10 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
                 position(sk, p);
             }
             // 0 <= p < fd as unsigned compares of the bits (test_march_kernel)
-            in[k] = ((int)valid & (int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
-                     (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
-                     (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            in[k] = ((int)valid & (int)(__float_as_uint(p[0]) < __float_as_uint(CROP ? bx.hi[0] : f.fd1)) &
+                     (int)(__float_as_uint(p[1]) < __float_as_uint(CROP ? bx.hi[1] : f.fd2)) &
+                     (int)(__float_as_uint(p[2]) < __float_as_uint(CROP ? bx.hi[2] : f.fd3))) != 0;
+            if (CROP) in[k] = ((int)in[k] & (int)crop_lower<CROP>(bx, p[0], p[1], p[2])) != 0;
             any_in |= in[k];
             int i0[3];
 #pragma unroll
@@ -321,9 +329,12 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
                     const float len2 = (gx * gx + gy * gy) + gz * gz;
                     const float mag = sqrtf(len2);
                     // gradient opacity G(mag), with or without a normal
+                    // (CROP without SEP: the three matrices, G and the box together passed the scalar registers
+                    // by enough to leave two instantiations a stack slot; there the m_i are read from the LDS
+                    // table -- the same floats -- and the 16 SGPRs go to the rest)
                     int jg = 0;   // the points m_i <= mag (a NaN: none)
 #pragma unroll
-                    for (int i = 0; i < kMaxGopa; ++i) jg += (int)(mag >= h.m[i]);
+                    for (int i = 0; i < kMaxGopa; ++i) jg += (int)(mag >= ((CROP && !SEP) ? s_G[i].x : h.m[i]));
                     const float4 ge = s_G[max(jg - 1, 0)];
                     const float ug = fminf((mag - ge.x) * ge.y, 1.0f);
                     const float ug1 = 1.0f - ug;
@@ -411,17 +422,20 @@ size_t cmap_lds_bytes(const TestFrame& f, const CmapFrame& g, bool ess, bool sha
            ((f.sep && f.sep_tab) ? (size_t)(f.S + 2 * kCmapK) * sizeof(float4) : 0);
 }
 
-// shade: the coefficients and G of an SCDVR frame, or null for a CDVR frame (whose kernels read none)
+// shade: the coefficients and G of an SCDVR frame, or null for a CDVR frame (whose kernels read none);
+// crop: the effective crop box, or null with the box off (the CROP = false instantiations)
 hipError_t launch_cmap_march(const TestFrame& f, const CmapFrame& g, const ScdvrFrame* shade, const WorkTile* work,
                              int n_blocks, const void* vol, bool u8, const float2* xi, const float4* col,
-                             const uint32_t* occ, float4* out, hipStream_t st) {
+                             const uint32_t* occ, float4* out, hipStream_t st, const CropBox* crop) {
     const bool f2b = (f.flags & 2) != 0, ess = (f.flags & 1) != 0 && f.zero_transparent && occ != nullptr;
     const bool small = g.n <= kCmapSmall, sep = f.sep != 0;
     const size_t lds = cmap_lds_bytes(f, g, ess, shade != nullptr);
     const ScdvrFrame h = shade ? *shade : ScdvrFrame{};
-#define VR_C6(F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_)                                                                 \
-    hipLaunchKernelGGL((cmap_march_kernel<F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_>), dim3(n_blocks), dim3(kWgThreads), \
-                       lds, st, f, g, h, work, vol, xi, col, occ, out)
+    const CropBox cb = crop ? *crop : CropBox{};
+#define VR_C7(F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_, CROP_)                                                 \
+    hipLaunchKernelGGL((cmap_march_kernel<F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_, CROP_>), dim3(n_blocks),    \
+                       dim3(kWgThreads), lds, st, f, g, h, work, vol, xi, col, occ, out, cb)
+#define VR_C6(F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_) do { if (crop) VR_C7(F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_, true); else VR_C7(F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_, false); } while (0)
 #define VR_C5(F2B_, ESS_, U8_, SMALL_, SEP_) do { if (shade) VR_C6(F2B_, ESS_, U8_, SMALL_, SEP_, true); else VR_C6(F2B_, ESS_, U8_, SMALL_, SEP_, false); } while (0)
 #define VR_C4(F2B_, ESS_, U8_, SMALL_) do { if (sep) VR_C5(F2B_, ESS_, U8_, SMALL_, true); else VR_C5(F2B_, ESS_, U8_, SMALL_, false); } while (0)
 #define VR_C3(F2B_, ESS_, U8_) do { if (small) VR_C4(F2B_, ESS_, U8_, true); else VR_C4(F2B_, ESS_, U8_, false); } while (0)
@@ -433,6 +447,7 @@ hipError_t launch_cmap_march(const TestFrame& f, const CmapFrame& g, const Scdvr
 #undef VR_C4
 #undef VR_C5
 #undef VR_C6
+#undef VR_C7
     return hipGetLastError();
 }
 

@@ -250,6 +250,16 @@ struct ScdvrFrame {
     float w[kMaxGopa];          // w[0 .. n), the rest w[n - 1]
 };
 
+// The crop box of the six field marches (vr_set_crop_box; their CROP instantiations read it, the others
+// ignore it), by value per launch like IsoFrame's values -- its own kernel argument, the last one, so
+// TestFrame and every argument offset of the CROP = false instantiations stay as they were.  The
+// effective box E = [max(lo, 0), min(hi, d)) per axis: "in the volume and in the box" is then
+// lo <= p < hi alone.  hi > 0 on every axis, or -- E empty on some axis -- lo = hi = +0 on all three,
+// which no position satisfies (the upper test is the unsigned compare of the bits, the lower p >= lo).
+struct CropBox {
+    float lo[3], hi[3];
+};
+
 // TransferFunction::getMaterial (TransferFunction.cu:46-55): last closed interval containing v, else 0
 __device__ __forceinline__ int tf_class(const float* lo, const float* hi, int n, float v) {
     int r = 0;

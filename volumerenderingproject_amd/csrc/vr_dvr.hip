@@ -52,17 +52,24 @@ namespace vr {
 // is never shaded: it stays the exact no-op of both blends that the empty-cell skip (ESS) and the
 // blank-batch skip rely on, so the cell bits and their margin are DVR's.  (No amdgpu_waves_per_eu
 // cap: profiles/sdvr/resource_usage.txt -- every instantiation fits without scratch left to itself.)
+//
+// CROP (vr_set_crop_box; cb is read by these instantiations only): "in the volume" is "in the volume and
+// in the box" -- cb is the effective box [max(lo, 0), min(hi, d)), whose upper bounds stand in fd's place
+// in the unsigned-bits compare and whose lower bounds add three compares (crop_lower) -- in in[k], hence
+// in the colour, the gathers and SHADE's lit samples, and in the ESS first-sample test; the ray range
+// comes from crop_clip.  The field (corners, clamps, gradient taps, the light) is the whole volume's.
+// The CROP = false instantiations are the kernels without the flag, instruction for instruction.
 // ------------------------------------------------------------------------------------------------
 constexpr int kDvrK = 4;
 
-template <bool F2B, bool ESS, bool U8, bool SEG8, bool SEP, bool SHADE>
+template <bool F2B, bool ESS, bool U8, bool SEG8, bool SEP, bool SHADE, bool CROP>
 __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g, SdvrFrame h,
                                                         const WorkTile* __restrict__ work,
                                                         const void* __restrict__ vol,
                                                         const float* __restrict__ gstart,
                                                         const float4* __restrict__ gseg,
                                                         const uint32_t* __restrict__ gocc,
-                                                        float4* __restrict__ out) {
+                                                        float4* __restrict__ out, CropBox cb) {
     constexpr int K = kDvrK;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // LDS: the segments' colours | their starts (search only) | the cell bits (ESS) | the B table (SEP)
@@ -138,7 +145,8 @@ __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g,
         float pb[3];
         position(0, pa);
         position(f.S > 1 ? f.S - 1 : 0, pb);
-        test_clip(f, pa, pb, dp, idp, s_begin, s_end);
+        if (CROP) crop_clip(f, cb, pa, pb, dp, idp, s_begin, s_end);
+        else test_clip(f, pa, pb, dp, idp, s_begin, s_end);
         if (SHADE) {   // headlight along the ray, in voxel space (iso_march_kernel's, from the same two end points)
             const float ex = pb[0] - pa[0], ey = pb[1] - pa[1], ez = pb[2] - pa[2];
             const float n2 = (ex * ex + ey * ey) + ez * ez;
@@ -167,9 +175,11 @@ __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g,
             float* p = pfirst;
             position(s, p);
             // (bitwise, not short-circuit: && chains compile to exec-mask branches)
-            const bool inside = ((int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
-                                 (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
-                                 (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            bool inside = ((int)(__float_as_uint(p[0]) < __float_as_uint(CROP ? cb.hi[0] : f.fd1)) &
+                           (int)(__float_as_uint(p[1]) < __float_as_uint(CROP ? cb.hi[1] : f.fd2)) &
+                           (int)(__float_as_uint(p[2]) < __float_as_uint(CROP ? cb.hi[2] : f.fd3))) != 0;
+            // CROP: the effective box's upper bounds stand in fd's place; its lower compares (vr_march.h)
+            if (CROP) inside = ((int)inside & (int)crop_lower<CROP>(cb, p[0], p[1], p[2])) != 0;
             int cc[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) cc[c] = inside ? ((int)p[c] >> f.tcb) : 0;
@@ -194,9 +204,10 @@ __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g,
                 position(sk, p);
             }
             // 0 <= p < fd as unsigned compares of the bits (test_march_kernel)
-            in[k] = ((int)valid & (int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
-                     (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
-                     (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            in[k] = ((int)valid & (int)(__float_as_uint(p[0]) < __float_as_uint(CROP ? cb.hi[0] : f.fd1)) &
+                     (int)(__float_as_uint(p[1]) < __float_as_uint(CROP ? cb.hi[1] : f.fd2)) &
+                     (int)(__float_as_uint(p[2]) < __float_as_uint(CROP ? cb.hi[2] : f.fd3))) != 0;
+            if (CROP) in[k] = ((int)in[k] & (int)crop_lower<CROP>(cb, p[0], p[1], p[2])) != 0;
             any_in |= in[k];
             int i0[3];
 #pragma unroll
@@ -429,17 +440,20 @@ size_t dvr_lds_bytes(const TestFrame& f, const DvrFrame& g, bool ess) {
            ((f.sep && f.sep_tab) ? (size_t)(f.S + 2 * kDvrK) * sizeof(float4) : 0);
 }
 
-// shade: the coefficients of an SDVR frame, or null for a DVR frame (whose kernels read none)
+// shade: the coefficients of an SDVR frame, or null for a DVR frame (whose kernels read none);
+// crop: the effective crop box, or null with the box off (the CROP = false instantiations)
 hipError_t launch_dvr_march(const TestFrame& f, const DvrFrame& g, const SdvrFrame* shade, const WorkTile* work,
                             int n_blocks, const void* vol, bool u8, const float* start, const float4* seg,
-                            const uint32_t* occ, float4* out, hipStream_t st) {
+                            const uint32_t* occ, float4* out, hipStream_t st, const CropBox* crop) {
     const bool f2b = (f.flags & 2) != 0, ess = (f.flags & 1) != 0 && f.zero_transparent && occ != nullptr;
     const bool seg8 = g.nseg <= 1 + kDvrSeg8, sep = f.sep != 0;
     const size_t lds = dvr_lds_bytes(f, g, ess);
     const SdvrFrame h = shade ? *shade : SdvrFrame{};
-#define VR_D6(F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_)                                                                \
-    hipLaunchKernelGGL((dvr_march_kernel<F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_>), dim3(n_blocks), dim3(kWgThreads), \
-                       lds, st, f, g, h, work, vol, start, seg, occ, out)
+    const CropBox cb = crop ? *crop : CropBox{};
+#define VR_D7(F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_, CROP_)                                                  \
+    hipLaunchKernelGGL((dvr_march_kernel<F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_, CROP_>), dim3(n_blocks),      \
+                       dim3(kWgThreads), lds, st, f, g, h, work, vol, start, seg, occ, out, cb)
+#define VR_D6(F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_) do { if (crop) VR_D7(F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_, true); else VR_D7(F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_, false); } while (0)
 #define VR_D5(F2B_, ESS_, U8_, SEG8_, SEP_) do { if (shade) VR_D6(F2B_, ESS_, U8_, SEG8_, SEP_, true); else VR_D6(F2B_, ESS_, U8_, SEG8_, SEP_, false); } while (0)
 #define VR_D4(F2B_, ESS_, U8_, SEG8_) do { if (sep) VR_D5(F2B_, ESS_, U8_, SEG8_, true); else VR_D5(F2B_, ESS_, U8_, SEG8_, false); } while (0)
 #define VR_D3(F2B_, ESS_, U8_) do { if (seg8) VR_D4(F2B_, ESS_, U8_, true); else VR_D4(F2B_, ESS_, U8_, false); } while (0)
@@ -451,6 +465,7 @@ hipError_t launch_dvr_march(const TestFrame& f, const DvrFrame& g, const SdvrFra
 #undef VR_D4
 #undef VR_D5
 #undef VR_D6
+#undef VR_D7
     return hipGetLastError();
 }
 

@@ -35,6 +35,11 @@ namespace vr {
 // ray against the hundreds of the march.  Fractional sample coordinates take the per-sample
 // expressions of the position chain (test_B_entry under SEP; the LDS table holds integer samples only,
 // and equals those expressions bit for bit there).
+//
+// CROP (vr_set_crop_box; cb is read by these instantiations only): iso_inside tests the volume and the
+// box at all of its uses -- the hit test (and the ESS first-sample test), sample s_h - 1 and every
+// bisection midpoint -- and crop_clip gives the ray range.  The gradient taps and the light read the
+// whole volume: the cut face sits at the first in-box sample and is shaded by the data's gradient.
 // ------------------------------------------------------------------------------------------------
 constexpr int kIsoK = 4;
 
@@ -60,18 +65,24 @@ __device__ __forceinline__ void iso_position(const TestFrame& f, const TestRay& 
     mulv3(f.tv, q2[0], q2[1], q2[2], p);
 }
 
-// 0 <= p < fd per axis as unsigned compares of the bits (test_march_kernel)
-__device__ __forceinline__ bool iso_inside(const TestFrame& f, float px, float py, float pz) {
-    return ((int)(__float_as_uint(px) < __float_as_uint(f.fd1)) & (int)(__float_as_uint(py) < __float_as_uint(f.fd2)) &
-            (int)(__float_as_uint(pz) < __float_as_uint(f.fd3))) != 0;
+// 0 <= p < fd per axis as unsigned compares of the bits (test_march_kernel); CROP: in the volume and in
+// the box -- the effective box's upper bounds in fd's place and its lower compares (vr_march.h) -- at
+// every use: the hit test, sample s_h - 1 and the bisection midpoints
+template <bool CROP>
+__device__ __forceinline__ bool iso_inside(const TestFrame& f, const CropBox& cb, float px, float py, float pz) {
+    bool in = ((int)(__float_as_uint(px) < __float_as_uint(CROP ? cb.hi[0] : f.fd1)) &
+               (int)(__float_as_uint(py) < __float_as_uint(CROP ? cb.hi[1] : f.fd2)) &
+               (int)(__float_as_uint(pz) < __float_as_uint(CROP ? cb.hi[2] : f.fd3))) != 0;
+    if (CROP) in = ((int)in & (int)crop_lower<CROP>(cb, px, py, pz)) != 0;
+    return in;
 }
 
 // (ESS, U8, SEP -- the flagship path -- allocates 80 VGPRs left to itself, 6 waves per SIMD where MIP's
 // twin has 7; held to 7 waves it fits 72 without scratch.  The other instantiations are left alone.)
-template <bool ESS, bool U8, bool SEP>
+template <bool ESS, bool U8, bool SEP, bool CROP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ESS && U8 && SEP ? 7 : 1)))
 void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work, const void* __restrict__ vol,
-                      const float* __restrict__ gbound, float4* __restrict__ out) {
+                      const float* __restrict__ gbound, float4* __restrict__ out, CropBox cb) {
     constexpr int K = kIsoK;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float4* s_B = reinterpret_cast<float4*>(smem);   // LDS: the B table (SEP) only
@@ -95,7 +106,9 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
         float pb[3];
         position(0, pa);
         position(f.S > 1 ? f.S - 1 : 0, pb);
-        test_clip(f, pa, pb, dp, idp, s_begin, s_end);   // (host: zero_transparent = 1, the clip always holds)
+        // (host: zero_transparent = 1, the clip always holds)
+        if (CROP) crop_clip(f, cb, pa, pb, dp, idp, s_begin, s_end);
+        else test_clip(f, pa, pb, dp, idp, s_begin, s_end);
     }
 
     // (host: the array is addressable with 32-bit byte offsets)
@@ -114,7 +127,7 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
             float* p = pfirst;
             position(s, p);
             // (bitwise, not short-circuit: && chains compile to exec-mask branches)
-            const bool inside = iso_inside(f, p[0], p[1], p[2]);
+            const bool inside = iso_inside<CROP>(f, cb, p[0], p[1], p[2]);
             int cc[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) cc[c] = inside ? ((int)p[c] >> f.tcb) : 0;
@@ -138,7 +151,7 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
             } else {
                 position(sk, p);
             }
-            in[k] = ((int)(sk < s_end) & (int)iso_inside(f, p[0], p[1], p[2])) != 0;
+            in[k] = ((int)(sk < s_end) & (int)iso_inside<CROP>(f, cb, p[0], p[1], p[2])) != 0;
             any_in |= in[k];
             int i0[3];
 #pragma unroll
@@ -218,7 +231,7 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
         if (sh > 0) {
             float pp[3];
             iso_position<SEP>(f, ray, (float)(sh - 1), pp);
-            refinable = iso_inside(f, pp[0], pp[1], pp[2]);
+            refinable = iso_inside<CROP>(f, cb, pp[0], pp[1], pp[2]);
             lo = refinable ? (float)(sh - 1) : hi;
         }
 #pragma unroll 1
@@ -226,7 +239,7 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
             const float mid = (lo + hi) * 0.5f;
             float pm[3];
             iso_position<SEP>(f, ray, mid, pm);
-            const bool ok = iso_inside(f, pm[0], pm[1], pm[2]);
+            const bool ok = iso_inside<CROP>(f, cb, pm[0], pm[1], pm[2]);
             const float v = field_value_at<U8>(ok, pm[0], pm[1], pm[2], vrs, d3, d23, xl, yl, zl);
             const bool take = ok && v >= iso;
             hi = (refinable && take) ? mid : hi;
@@ -287,18 +300,21 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
 // ------------------------------------------------------------------------------------------------
 
 hipError_t launch_iso_march(const TestFrame& f, const IsoFrame& g, const WorkTile* work, int n_blocks, const void* vol,
-                            bool u8, const float* bound, float4* out, hipStream_t st) {
+                            bool u8, const float* bound, float4* out, hipStream_t st, const CropBox* crop) {
     const bool ess = (f.flags & 1) != 0 && bound != nullptr, sep = f.sep != 0;
+    const CropBox cb = crop ? *crop : CropBox{};   // (null: the box is off, the CROP = false instantiations)
     const size_t lds = (f.sep && f.sep_tab) ? (size_t)(f.S + 2 * kIsoK) * sizeof(float4) : 0;
-#define VR_I3(ESS_, U8_, SEP_)                                                                              \
-    hipLaunchKernelGGL((iso_march_kernel<ESS_, U8_, SEP_>), dim3(n_blocks), dim3(kWgThreads), lds, st, f, g, work, \
-                       vol, bound, out)
+#define VR_I4(ESS_, U8_, SEP_, CROP_)                                                                  \
+    hipLaunchKernelGGL((iso_march_kernel<ESS_, U8_, SEP_, CROP_>), dim3(n_blocks), dim3(kWgThreads), lds, st, f, \
+                       g, work, vol, bound, out, cb)
+#define VR_I3(ESS_, U8_, SEP_) do { if (crop) VR_I4(ESS_, U8_, SEP_, true); else VR_I4(ESS_, U8_, SEP_, false); } while (0)
 #define VR_I2(ESS_, U8_) do { if (sep) VR_I3(ESS_, U8_, true); else VR_I3(ESS_, U8_, false); } while (0)
 #define VR_I1(ESS_) do { if (u8) VR_I2(ESS_, true); else VR_I2(ESS_, false); } while (0)
     if (ess) VR_I1(true); else VR_I1(false);
 #undef VR_I1
 #undef VR_I2
 #undef VR_I3
+#undef VR_I4
     return hipGetLastError();
 }
 

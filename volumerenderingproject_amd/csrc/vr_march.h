@@ -237,6 +237,53 @@ __device__ __forceinline__ void test_clip(const TestFrame& f, const float pa[3],
     }
 }
 
+// The crop box (vr_set_crop_box; the CROP instantiations of the field marches).  cb is the effective box
+// E = [max(lo, 0), min(hi, d)) (vr_device.h CropBox), so "in the volume and in the box" is lo <= p < hi:
+// the marches put cb.hi in the place of (fd1, fd2, fd3) in their unsigned-bits compare -- the interval
+// test against d and the one against hi are together the one against min(hi, d), exactly -- and add the
+// three lower compares below (float compares of the position itself; a NaN is outside).  Without CROP
+// the constant true, which the bitwise chains fold away.
+template <bool CROP>
+__device__ __forceinline__ bool crop_lower(const CropBox& cb, float px, float py, float pz) {
+    if (!CROP) return true;
+    return ((int)(px >= cb.lo[0]) & (int)(py >= cb.lo[1]) & (int)(pz >= cb.lo[2])) != 0;
+}
+
+// test_clip against E in the volume's place: the same linear model, E widened by the same 0.01 voxel, the
+// same floor - 1 / ceil + 2 margins (E lies in the volume, so the same bounds on the model's error hold),
+// and like test_clip it narrows the range only under zero_transparent -- otherwise the samples outside
+// the box are TF(0) fog, and every one of them is blended.  Samples outside [s_begin, s_end) are outside
+// E: not in the box, or not in the volume.
+__device__ __forceinline__ void crop_clip(const TestFrame& f, const CropBox& cb, const float pa[3], const float pb[3],
+                                          float dp[3], float idp[3], int& s_begin, int& s_end) {
+    s_begin = 0;
+    s_end = f.S;
+    const float den = (float)(f.S > 1 ? f.S - 1 : 1);
+    float a = 0.0f, bnd = (float)(f.S - 1);
+    bool off = false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        dp[c] = f.S > 1 ? (pb[c] - pa[c]) / den : 0.0f;
+        idp[c] = dp[c] != 0.0f ? 1.0f / dp[c] : 0.0f;
+        const float lo = cb.lo[c] - 0.01f, hi = cb.hi[c] + 0.01f;
+        if (dp[c] == 0.0f) {
+            off |= (pa[c] < lo) | (pa[c] > hi);
+        } else {
+            const float t0 = (lo - pa[c]) * idp[c], t1 = (hi - pa[c]) * idp[c];
+            a = fmaxf(a, fminf(t0, t1));
+            bnd = fminf(bnd, fmaxf(t0, t1));
+        }
+    }
+    if (f.zero_transparent) {
+        if (off || !(a <= bnd)) {
+            s_end = 0;
+        } else {
+            s_begin = max(0, (int)floorf(a) - 1);
+            s_end = min(f.S, (int)ceilf(bnd) + 2);
+        }
+    }
+}
+
 // ESS: sample s lies in the empty macro cell cc (2^tcb voxels per axis): the next sample in march
 // order past the cell, from the linear model with a 0.05-voxel safety margin (which covers the
 // model's rounding), so every skipped sample lies inside the cell.

@@ -41,14 +41,19 @@ namespace vr {
 // margin that bound lies above the volume's largest voxel, which is as far as a running maximum gets
 // but for the lerps' last ulps: the stop is exact and all but never taken (C3: ESS | ERT times equal
 // ESS, profiles/mip/probe.json).
+//
+// CROP (vr_set_crop_box; cb is read by these instantiations only): the maximum runs over the samples in
+// the volume and in the box -- the effective box in the volume's place in in[k] and in the ESS
+// first-sample test (dvr_march_kernel's CROP), crop_clip for the ray range.  A cell's bound still bounds
+// every sample based in it, in the box or not, so the skip and the stop are unchanged.
 // ------------------------------------------------------------------------------------------------
 constexpr int kMipK = 4;
 
-template <bool ESS, bool U8, bool SEP>
+template <bool ESS, bool U8, bool SEP, bool CROP>
 __global__ __launch_bounds__(256) void mip_march_kernel(TestFrame f, MipFrame g, const WorkTile* __restrict__ work,
                                                         const void* __restrict__ vol,
                                                         const float* __restrict__ gbound,
-                                                        float4* __restrict__ out) {
+                                                        float4* __restrict__ out, CropBox cb) {
     constexpr int K = kMipK;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float4* s_B = reinterpret_cast<float4*>(smem);   // LDS: the B table (SEP) only
@@ -72,7 +77,9 @@ __global__ __launch_bounds__(256) void mip_march_kernel(TestFrame f, MipFrame g,
         float pb[3];
         position(0, pa);
         position(f.S > 1 ? f.S - 1 : 0, pb);
-        test_clip(f, pa, pb, dp, idp, s_begin, s_end);   // (host: zero_transparent = 1, the clip always holds)
+        // (host: zero_transparent = 1, the clip always holds)
+        if (CROP) crop_clip(f, cb, pa, pb, dp, idp, s_begin, s_end);
+        else test_clip(f, pa, pb, dp, idp, s_begin, s_end);
     }
 
     // (host: the array is addressable with 32-bit byte offsets)
@@ -93,9 +100,11 @@ __global__ __launch_bounds__(256) void mip_march_kernel(TestFrame f, MipFrame g,
             float* p = pfirst;
             position(s, p);
             // (bitwise, not short-circuit: && chains compile to exec-mask branches)
-            const bool inside = ((int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
-                                 (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
-                                 (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            bool inside = ((int)(__float_as_uint(p[0]) < __float_as_uint(CROP ? cb.hi[0] : f.fd1)) &
+                           (int)(__float_as_uint(p[1]) < __float_as_uint(CROP ? cb.hi[1] : f.fd2)) &
+                           (int)(__float_as_uint(p[2]) < __float_as_uint(CROP ? cb.hi[2] : f.fd3))) != 0;
+            // CROP: the effective box's upper bounds stand in fd's place; its lower compares (vr_march.h)
+            if (CROP) inside = ((int)inside & (int)crop_lower<CROP>(cb, p[0], p[1], p[2])) != 0;
             int cc[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) cc[c] = inside ? ((int)p[c] >> f.tcb) : 0;
@@ -120,9 +129,10 @@ __global__ __launch_bounds__(256) void mip_march_kernel(TestFrame f, MipFrame g,
                 position(sk, p);
             }
             // 0 <= p < fd as unsigned compares of the bits (test_march_kernel)
-            in[k] = ((int)(sk < s_end) & (int)(__float_as_uint(p[0]) < __float_as_uint(f.fd1)) &
-                     (int)(__float_as_uint(p[1]) < __float_as_uint(f.fd2)) &
-                     (int)(__float_as_uint(p[2]) < __float_as_uint(f.fd3))) != 0;
+            in[k] = ((int)(sk < s_end) & (int)(__float_as_uint(p[0]) < __float_as_uint(CROP ? cb.hi[0] : f.fd1)) &
+                     (int)(__float_as_uint(p[1]) < __float_as_uint(CROP ? cb.hi[1] : f.fd2)) &
+                     (int)(__float_as_uint(p[2]) < __float_as_uint(CROP ? cb.hi[2] : f.fd3))) != 0;
+            if (CROP) in[k] = ((int)in[k] & (int)crop_lower<CROP>(cb, p[0], p[1], p[2])) != 0;
             any_in |= in[k];
             int i0[3];
 #pragma unroll
@@ -226,18 +236,21 @@ __global__ __launch_bounds__(256) void mip_bounds_kernel(const float2* __restric
 // ------------------------------------------------------------------------------------------------
 
 hipError_t launch_mip_march(const TestFrame& f, const MipFrame& g, const WorkTile* work, int n_blocks, const void* vol,
-                            bool u8, const float* bound, float4* out, hipStream_t st) {
+                            bool u8, const float* bound, float4* out, hipStream_t st, const CropBox* crop) {
     const bool ess = (f.flags & 1) != 0 && bound != nullptr, sep = f.sep != 0;
+    const CropBox cb = crop ? *crop : CropBox{};   // (null: the box is off, the CROP = false instantiations)
     const size_t lds = (f.sep && f.sep_tab) ? (size_t)(f.S + 2 * kMipK) * sizeof(float4) : 0;
-#define VR_M3(ESS_, U8_, SEP_)                                                                              \
-    hipLaunchKernelGGL((mip_march_kernel<ESS_, U8_, SEP_>), dim3(n_blocks), dim3(kWgThreads), lds, st, f, g, work, \
-                       vol, bound, out)
+#define VR_M4(ESS_, U8_, SEP_, CROP_)                                                                  \
+    hipLaunchKernelGGL((mip_march_kernel<ESS_, U8_, SEP_, CROP_>), dim3(n_blocks), dim3(kWgThreads), lds, st, f, \
+                       g, work, vol, bound, out, cb)
+#define VR_M3(ESS_, U8_, SEP_) do { if (crop) VR_M4(ESS_, U8_, SEP_, true); else VR_M4(ESS_, U8_, SEP_, false); } while (0)
 #define VR_M2(ESS_, U8_) do { if (sep) VR_M3(ESS_, U8_, true); else VR_M3(ESS_, U8_, false); } while (0)
 #define VR_M1(ESS_) do { if (u8) VR_M2(ESS_, true); else VR_M2(ESS_, false); } while (0)
     if (ess) VR_M1(true); else VR_M1(false);
 #undef VR_M1
 #undef VR_M2
 #undef VR_M3
+#undef VR_M4
     return hipGetLastError();
 }
 

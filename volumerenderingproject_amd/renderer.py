@@ -53,6 +53,7 @@ EXPORTED = [
     "vr_axis_columns_plan", "vr_tf_segments", "vr_set_isosurface", "vr_get_isosurface",
     "vr_set_colormap", "vr_get_colormap", "vr_colormap_eval",
     "vr_set_gradient_opacity", "vr_get_gradient_opacity", "vr_gradient_opacity_eval",
+    "vr_set_crop_box", "vr_get_crop_box",
 ]
 VR_COMM_ID_BYTES = 128
 VR_TRANSPORT_NONE, VR_TRANSPORT_RCCL, VR_TRANSPORT_PEER_COPY = 0, 1, 2
@@ -190,6 +191,8 @@ def lib():
         "vr_set_transfer_function": ([vp, P(TFInterval), C.c_int32], C.c_int),
         "vr_set_isosurface": ([vp, C.c_float, P(C.c_float)], C.c_int),
         "vr_get_isosurface": ([vp, P(C.c_float), P(C.c_float)], C.c_int),
+        "vr_set_crop_box": ([vp, P(C.c_float), P(C.c_float)], C.c_int),
+        "vr_get_crop_box": ([vp, P(C.c_float), P(C.c_float), P(C.c_int32)], C.c_int),
         "vr_set_colormap": ([vp, P(CmapPoint), C.c_int32], C.c_int),
         "vr_get_colormap": ([vp, P(CmapPoint), C.c_int32, P(C.c_int32)], C.c_int),
         "vr_colormap_eval": ([P(CmapPoint), C.c_int32, P(C.c_float), C.c_int64, P(C.c_float)], C.c_int),
@@ -549,6 +552,25 @@ class VolumeRenderer:
         iso, c = C.c_float(), (C.c_float * 3)()
         _check(lib().vr_get_isosurface(self._ctx, C.byref(iso), c), "vr_get_isosurface")
         return iso.value, (c[0], c[1], c[2])
+
+    def set_crop_box(self, lo, hi=None):
+        """The crop box of the six field modes: a sample takes part iff lo[a] <= p_a < hi[a] on every axis (voxel
+        coordinates, float32 compares); set_crop_box(None) turns it off.  Host state, nothing is rebuilt."""
+        if lo is None and hi is None:
+            _check(lib().vr_set_crop_box(self._ctx, None, None), "vr_set_crop_box")
+            return
+        if lo is None or hi is None:
+            raise ValueError("set_crop_box: lo and hi, or None")
+        a = (C.c_float * 3)(*[float(v) for v in lo])
+        b = (C.c_float * 3)(*[float(v) for v in hi])
+        _check(lib().vr_set_crop_box(self._ctx, a, b), "vr_set_crop_box")
+
+    @property
+    def crop_box(self):
+        """((lo), (hi)) as the context holds them (float32), or None with the box off."""
+        a, b, on = (C.c_float * 3)(), (C.c_float * 3)(), C.c_int32()
+        _check(lib().vr_get_crop_box(self._ctx, a, b, C.byref(on)), "vr_get_crop_box")
+        return ((a[0], a[1], a[2]), (b[0], b[1], b[2])) if on.value else None
 
     def set_colormap(self, points):
         """VR_MODE_CDVR's colour map: a sequence of (x, (r, g, b, a)), x in voxel units and strictly
