@@ -390,6 +390,15 @@ typedef struct {
                                   queued on those streams in turn, each beside the expand passes of
                                   the frames of the launch before.  0 = every march first, then the
                                   expands.  Launch order only: bitwise the same frames                */
+    int32_t column_fused;      /* the column path (axis_columns) in one kernel: a workgroup marches the
+                                  leaf columns under a tile of pixels (64 x 48 down to 16 x 16: the
+                                  largest with at most 256 columns under any tile) and stores the
+                                  tile, so no column buffer and no expand pass; vr_render_batch
+                                  renders its frames of this kind in launches of up to 32.  1 = on
+                                  (default), 0 = the column march and the expand pass as two kernels
+                                  (column_overlap).  A frame no tile shape fits, per-launch timing,
+                                  groups, tile and host-batch output take the two kernels.  Bitwise the
+                                  same frames                                                        */
 } vr_options;
 
 int vr_options_default(vr_options* out);
@@ -679,6 +688,13 @@ int vr_count_work(vr_ctx* ctx, const vr_params* params, const vr_camera* camera,
  * (ascending; 0 when the view is not axis-aligned or nothing is visible); out[3] = the pixels of the
  * visible rectangle. */
 int vr_axis_columns_plan(vr_ctx* ctx, const vr_params* params, const vr_camera* camera, int32_t out[4]);
+
+/* Whether vr_render would render this frame with the fused column march (vr_options.column_fused), decided
+ * on the host alone: out[0] x out[1] = the pixel tile of a workgroup, the largest of 64 x 48, 48 x 48,
+ * 48 x 32, 32 x 32, 32 x 16, 16 x 16 under which no tile has more than 256 leaf columns; 0, 0 = not fused
+ * (off the column path, no shape fits, the option is 0, or per-launch timing is on).  vr_render_batch
+ * renders the frames of a call it fuses in the smallest tile any of them has here. */
+int vr_column_fused_plan(vr_ctx* ctx, const vr_params* params, const vr_camera* camera, int32_t out[2]);
 
 int vr_synchronize(vr_ctx* ctx);
 /* Use an external HIP stream (hipStream_t passed as void*); NULL restores the ctx's own.  Work on the

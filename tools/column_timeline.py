@@ -9,7 +9,11 @@ marches, the span of the expands, the time during which both kinds are running, 
 duration with and without a march running beside them.  --show K also lists call K launch by launch with its stream (or
 queue) id; the summary line is over the calls with --frames expands (the steady ones).
 
-usage: python tools/column_timeline.py <kernel_trace.csv> [--frames 32] [--show K]"""
+--fused: the trace of a library that renders the calls' frames with the fused column march
+(vr_options.column_fused): no expand follows, so a call is the march launches whose frames add up to
+--frames; per call its launches, their durations, the span and the time some launch is running.
+
+usage: python tools/column_timeline.py <kernel_trace.csv> [--frames 32] [--show K] [--fused]"""
 import argparse
 import csv
 import statistics
@@ -38,11 +42,44 @@ def both(a, b):
     return t
 
 
+def fused_calls(rows, a):
+    calls, cur, n = [], [], 0
+    for _, s, e, kind, where, frames in rows:
+        if kind != "M":
+            continue
+        cur.append((s, e, where, frames))
+        n += frames
+        if n >= a.frames:
+            if n == a.frames:
+                calls.append(sorted(cur))
+            cur, n = [], 0
+    recs = []
+    for k, call in enumerate(calls):
+        t0, t1 = min(s for s, *_ in call), max(e for _, e, *_ in call)
+        u = union([(s, e) for s, e, *_ in call])
+        recs.append({"call": k, "launches": len(call), "span_us": (t1 - t0) / 1e3, "busy_us": sum(e - s for s, e in u) / 1e3,
+                     "durations_us": "/".join(f"{(e - s) / 1e3:.1f}x{fr}" for s, e, _, fr in call)})
+        if a.show == k:
+            for s, e, where, fr in call:
+                print(f"  F stream {where:>4}  frames {fr:3d}  start {(s - t0) / 1e3:8.2f} us  end {(e - t0) / 1e3:8.2f} us  "
+                      f"dur {(e - s) / 1e3:6.2f} us")
+        print(" ".join(f"{key}={v:.2f}" if isinstance(v, float) else f"{key}={v}" for key, v in recs[-1].items()))
+    if recs:
+        print(f"fused ({len(recs)} calls of {a.frames} frames), medians:")
+        for key in ("launches", "span_us", "busy_us"):
+            print(f"  {key} {statistics.median(r[key] for r in recs):.2f}")
+        print(f"  span per frame {statistics.median(r['span_us'] for r in recs) / a.frames:.2f} us")
+        gaps = [calls[i + 1][0][0] - max(e for _, e, *_ in calls[i]) for i in range(len(calls) - 1)]
+        if gaps:
+            print(f"  idle between calls {statistics.median(gaps) / 1e3:.2f} us")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("csv")
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--show", type=int, default=None)
+    ap.add_argument("--fused", action="store_true")
     a = ap.parse_args()
     rows = []
     for r in csv.DictReader(open(a.csv)):
@@ -52,6 +89,9 @@ def main():
             frames = int(r["Grid_Size_Y"]) // max(1, int(r["Workgroup_Size_Y"]))
             rows.append((int(r["Dispatch_Id"]), int(r["Start_Timestamp"]), int(r["End_Timestamp"]), kind, where, frames))
     rows.sort()
+    if a.fused:
+        fused_calls(rows, a)
+        return
     calls, cur, pending = [], [], 0
     for _, s, e, kind, where, frames in rows:
         cur.append((s, e, kind, where))

@@ -2,9 +2,9 @@
 stream is held busy (torch.cuda._sleep), so the host is out of the timed window (events on the caller's
 stream either side of the calls).  Prints one JSON line: per vr_options.column_overlap value (-1 = the
 library's default; the only value a library without the option takes) the min, median and max of seven
-repetitions, in us per frame.
+repetitions, in us per frame.  A second list gives vr_options.column_fused values (keys "overlap/fused").
 
-usage: python tools/device_only_time.py 0,1"""
+usage: python tools/device_only_time.py 0,1 [0,1]"""
 import json
 import os
 import sys
@@ -16,7 +16,9 @@ def main():
     import torch
     import volumerenderingproject_amd as vr
     from volumerenderingproject_amd import volumes
-    vals = [int(x) for x in sys.argv[1].split(",")]
+    vals = [(int(x), None) for x in sys.argv[1].split(",")]
+    if len(sys.argv) > 2:
+        vals = [(ov, int(fv)) for ov, _ in vals for fv in sys.argv[2].split(",")]
     vol, cal = volumes.mni152_standin()
     W, H, S = 1920, 1080, 500
     n, calls = 32, 8
@@ -24,10 +26,12 @@ def main():
     frames = torch.empty((n, W, H, 4), dtype=torch.float32, device="cuda:0")
     cams = (vr.Camera * n)(*([vr.default_camera(W, H)] * n))
     out = {}
-    for ov in vals:
+    for ov, fv in vals:
         o = vr.default_options()
         if ov >= 0:
             o.column_overlap = ov
+        if fv is not None:
+            o.column_fused = fv
         r = vr.VolumeRenderer(vol, cal, device=0, options=o)
         stream = torch.cuda.Stream(device=0)
         torch.cuda.set_stream(stream)
@@ -46,7 +50,7 @@ def main():
             torch.cuda.synchronize()
             res.append(e0.elapsed_time(e1) * 1e3 / (n * calls))
         res.sort()
-        out[str(ov)] = {"min": round(res[0], 3), "median": round(res[len(res) // 2], 3), "max": round(res[-1], 3)}
+        out[str(ov) if fv is None else f"{ov}/{fv}"] = {"min": round(res[0], 3), "median": round(res[len(res) // 2], 3), "max": round(res[-1], 3)}
         r.set_stream(0)
         r.close()
     print(json.dumps({"device_us_per_frame": out, "lib": os.path.basename(os.environ.get("VR_LIB") or "libvr.so")}))

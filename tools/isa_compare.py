@@ -102,6 +102,8 @@ def main():
     A, B = kernels(o.a), kernels(o.b)
     bk = {}
     for name in B:
+        if trailing is None and name in A:   # (the same kernel in both files: paired by its name, below)
+            continue
         k = key_of(name, trailing)
         if k is None:
             continue
@@ -111,6 +113,8 @@ def main():
     counts = {"identical": 0, "labels": 0, "different": 0, "unpaired": 0}
     for name in sorted(A, key=lambda n: key_of(n)[0]):
         shown, key = key_of(name)
+        if trailing is None and name in B:
+            bk[key] = (shown, name)
         if key not in bk:
             print("%s: NO PARTNER in %s" % (shown, o.b))
             counts["unpaired"] += 1

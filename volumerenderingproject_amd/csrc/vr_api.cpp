@@ -47,6 +47,8 @@ hipError_t launch_vrc_columns(const VrcFrame*, int, int, const uint8_t*, const i
                               hipStream_t, int, const unsigned long long*, const int32_t*, int32_t*,
                               const VrcFrame* dev_frames = nullptr);
 hipError_t launch_axis_expand(const VrcFrame&, const WorkTile*, int, int, int, const float4*, float4*, hipStream_t);
+hipError_t launch_vrc_fused(const VrcFrame*, int, int, const uint8_t*, const int32_t*, const float4*, int, float4*,
+                            hipStream_t, int, const unsigned long long*, const int32_t*, const VrcFrame*);
 size_t vrc_axis1_table_bytes(const VrcFrame&, int);
 int vrc_batch_of(const VrcFrame&, int);
 hipError_t launch_vrc_stats(const VrcFrame&, const WorkTile*, const int32_t*, int, const uint8_t*, const int32_t*,
@@ -625,6 +627,7 @@ void check_options(const vr_options& o) {
     if (o.leaf_columns < 0 || o.leaf_columns > 1) throw Error(VR_EINVAL, "vr_options: leaf_columns must be 0 or 1");
     if (o.axis_columns < 0 || o.axis_columns > 2) throw Error(VR_EINVAL, "vr_options: axis_columns must be 0, 1 or 2");
     if (o.column_overlap < 0 || o.column_overlap > 1) throw Error(VR_EINVAL, "vr_options: column_overlap must be 0 or 1");
+    if (o.column_fused < 0 || o.column_fused > 1) throw Error(VR_EINVAL, "vr_options: column_fused must be 0 or 1");
     if (o.dvr_volume < 0 || o.dvr_volume > 1) throw Error(VR_EINVAL, "vr_options: dvr_volume must be 0 or 1");
     if (o.farm_tile <= 0 || o.farm_tile % kWgRaysX || o.farm_tile > 4096)
         throw Error(VR_EINVAL, "vr_options: farm_tile must be a positive multiple of 16");
@@ -1624,6 +1627,77 @@ VrcFrame column_frame(const VrcFrame& f, const ColumnPlan& cp) {
     return fc;
 }
 
+// The fused column march (vr_options.column_fused; vrc_march_kernel, FUSE): the pixel-tile shapes, largest
+// first, each no larger than the one before on either side -- a shape that fits a frame fits with every
+// later one.  A shape fits when no tile can have more than kFuseCols leaf columns under it: between two
+// pixels of a tile the kernel's v (fuse_columns) on fixed axis a differs by at most d_a = (P - 1) |rsw /
+// W right_a| leaves + (Q - 1) |rsh / H up_a| leaves, up to the rounding of a handful of float operations
+// on values below 2 nleaf (under 1e-3 of a leaf for nleaf <= 2048), and values within d of each other
+// lie in at most floor(d) + 2 leaves.  -1: none fits.
+// Measured (profiles/column_fused/sweep.txt): launches over the in-flight streams in turn
+// beat the caller's stream alone by a tenth; a first launch of 6 frames ties one of 3 on the headline and
+// gains a tenth on a 19-frame call; 64 x 48 at the top of the ladder beats 48 x 48 and 48 x 32 in bench.py
+// (48 x 32 has the shortest device-only time, by 5 %, and loses 5 % with the host in the loop).
+// (VR_FUSE_TOP, VR_FUSE_FIRST, VR_FUSE_SCHED: -D knobs of the experiment builds only.)
+#ifndef VR_FUSE_TOP
+#define VR_FUSE_TOP 0
+#endif
+#ifndef VR_FUSE_FIRST
+#define VR_FUSE_FIRST 6
+#endif
+#ifndef VR_FUSE_SCHED
+#define VR_FUSE_SCHED 1
+#endif
+constexpr int kFuseLadder[][2] = {{64, 48}, {48, 48}, {48, 32}, {32, 32}, {32, 16}, {16, 16}};
+constexpr int kFuseShapes = (int)(sizeof kFuseLadder / sizeof kFuseLadder[0]);
+constexpr size_t kFuseFirst = VR_FUSE_FIRST;   // frames of a call's first launch (kernel arguments)
+constexpr int kFuseSched = VR_FUSE_SCHED;      // 0: every launch on the caller's stream; 1: over the in-flight streams in turn
+static_assert(VR_FUSE_TOP >= 0 && VR_FUSE_TOP < kFuseShapes && kFuseFirst >= 1 && kFuseFirst <= (size_t)kColBatch,
+              "the first launch's frames are kernel arguments");
+int fuse_shape(const VrcFrame& f) {
+    if (f.axis1 < 0 || f.conic) return -1;
+    const int ma = f.axis1, ax[2] = {ma == 0 ? 1 : 0, ma == 2 ? 1 : 2};
+    for (int s = VR_FUSE_TOP; s < kFuseShapes; ++s) {
+        int64_t cols = 1;
+        for (int j = 0; j < 2; ++j) {
+            const double dx = std::fabs((double)f.rsw / (double)f.W * (double)f.right[ax[j]]) * (double)f.leaves;
+            const double dy = std::fabs((double)f.rsh / (double)f.H * (double)f.up[ax[j]]) * (double)f.leaves;
+            const double d = (kFuseLadder[s][0] - 1) * dx + (kFuseLadder[s][1] - 1) * dy;
+            if (!(d < 1e6)) return -1;
+            cols *= (int64_t)std::floor(d * (1.0 + 1e-6) + 1e-3) + 2;
+        }
+        if (cols <= kFuseCols) return s;
+    }
+    return -1;
+}
+
+// The fused march's frame of a frame f that takes the column path with plan cp, in tiles of shape s:
+// f's own W x H, the column rectangle, and the tiling (FuseTiles) with the tiles that touch the visible
+// rectangle of 16 x 16 work tiles -- rect, or the whole frame -- first.  No work list.
+VrcFrame fused_frame(const VrcFrame& f, const ColumnPlan& cp, const TileRect& rect, int s) {
+    VrcFrame fc = f;
+    fc.col_i0 = cp.i0; fc.col_i1 = cp.i1; fc.col_n0 = cp.n0; fc.col_n1 = cp.n1;
+    fc.col_ofs = 0;
+    fc.n_hull = 0;
+    FuseTiles& t = fc.fuse;
+    t.P = kFuseLadder[s][0]; t.Q = kFuseLadder[s][1];
+    t.ntx = (f.W + t.P - 1) / t.P; t.nty = (f.H + t.Q - 1) / t.Q;
+    const int wtx = (f.W + kWgRaysX - 1) / kWgRaysX, wty = (f.H + kWgRaysY - 1) / kWgRaysY;
+    t.vtx0 = rect.all ? 0 : std::max(0, rect.tx0); t.vtx1 = rect.all ? wtx : std::min(wtx, rect.tx1 + 1);
+    t.vty0 = rect.all ? 0 : std::max(0, rect.ty0); t.vty1 = rect.all ? wty : std::min(wty, rect.ty1 + 1);
+    t.rx0 = t.ry0 = t.nrx = t.nry = 0;
+    if (t.vtx1 > t.vtx0 && t.vty1 > t.vty0) {
+        t.rx0 = t.vtx0 * kWgRaysX / t.P; t.nrx = (std::min(f.W, t.vtx1 * kWgRaysX) - 1) / t.P - t.rx0 + 1;
+        t.ry0 = t.vty0 * kWgRaysY / t.Q; t.nry = (std::min(f.H, t.vty1 * kWgRaysY) - 1) / t.Q - t.ry0 + 1;
+    }
+    fc.n_work = fc.n_slots = t.ntx * t.nty;
+    fc.persist_wgs = 0;
+    fc.out_tiles = 0; fc.out_rgb = 0;
+    fc.bg_first = INT32_MAX;
+    fc.bg_group = 1;
+    return fc;
+}
+
 // The expand pass's split of a frame's work list (launch_axis_expand), apart from the march's n_launch:
 // a whole frame's list, its culled entries from bg_first on, goes kExpandGroup rectangle entries and
 // kExpandBgGroup culled ones to a workgroup; any other list (tile output, a persistent grid's, no
@@ -1942,6 +2016,15 @@ void launch_frame(vr_ctx* c, const vr_params* p, const vr_camera* cam, const Wor
             f.col_i0 = pre->i0; f.col_i1 = pre->i1; f.col_n0 = pre->n0; f.col_n1 = pre->n1;
             const ExpandGrid eg = expand_grid(c, *wc, out_tiles);
             hip_check(launch_axis_expand(f, wc->work, eg.rect_end, eg.group, eg.bg_group, pre->buf, out, c->stream));
+        } else if (cp.take && c->opt.column_fused && !c->timing && fuse_shape(f) >= 0) {
+            // one fused launch: the tiles' columns marched and their pixels stored by the same workgroups
+            // (a published view table is staged, none is published: workgroup 0 may be a background tile)
+            const VrcFrame ff = fused_frame(f, cp, *rect, fuse_shape(f));
+            hip_check(launch_vrc_fused(&ff, 1, ff.n_work, vcls, vmaps, c->tf_rgba.as<float4>(), (int)c->tf.size(), out,
+                                       c->stream, c->batch,
+                                       (c->leafcols ? c->occ_leafcols : c->occ_cols).as<unsigned long long>(), gtab,
+                                       nullptr));
+            gtab_out = nullptr;
         } else if (cp.take) {
             // column march into this stream's column buffer, then the expand pass, in stream order: the
             // next frame of the stream overwrites the buffer only after this frame's expand has read it.
@@ -2329,6 +2412,7 @@ int vr_options_default(vr_options* o) {
     o->axis_columns = 1;
     o->dvr_volume = 0;
     o->column_overlap = 1;
+    o->column_fused = 1;
     return VR_OK;
 }
 
@@ -2680,6 +2764,58 @@ void chunk_columns(ColumnMarches& m, bool overlap) {
     }
 }
 
+// vr_render_batch, fused column path (vr_options.column_fused): the call's frames in axis_columns_plan's
+// scope that a tile shape fits and that share the first one's kernel variant, as fused frames (fused_frame)
+// in the smallest tile shape any of them needs -- a launch has one grid -- each storing its own frame of
+// the call's output (col_ofs).  done[i] is set for those; the others keep their own launch.  The launches:
+// the first kFuseFirst frames as kernel arguments, so that they wait for no upload, the rest from
+// c->colframes (upload_columns) in launches of up to kColFrames.
+void plan_fused(vr_ctx* c, const vr_params* p, const vr_camera* cams, int n, const std::vector<TileRect>& rects,
+                ColumnMarches& m, std::vector<char>& done) {
+    done.assign((size_t)n, 0);
+    if (n < 2 || !c->opt.column_fused || c->opt.axis_columns == 0 || p->mode != VR_MODE_VRC || c->timing) return;
+    std::vector<VrcFrame> fs;
+    std::vector<ColumnPlan> cps;
+    int shape = 0;
+    for (int i = 0; i < n; ++i) {
+        const VrcFrame f = make_vrc_march(c, p, &cams[i]);
+        const ColumnPlan cp = axis_columns_plan(c, p, f, rects[(size_t)i]);
+        const int s = cp.take ? fuse_shape(f) : -1;
+        if (s < 0) continue;
+        if (!fs.empty() && (f.axis1 != fs[0].axis1 || f.tsplit != fs[0].tsplit || f.zrun != fs[0].zrun)) continue;
+        shape = std::max(shape, s);
+        fs.push_back(f);
+        cps.push_back(cp);
+        m.idx.push_back(i);
+    }
+    for (size_t k = 0; k < fs.size(); ++k) {
+        VrcFrame ff = fused_frame(fs[k], cps[k], rects[(size_t)m.idx[k]], shape);
+        ff.col_ofs = (int64_t)m.idx[k] * p->width * p->height;
+        m.grid = ff.n_work;
+        m.fcs.push_back(ff);
+        done[(size_t)m.idx[k]] = 1;
+    }
+    if (m.fcs.empty()) return;
+    const size_t nf = m.fcs.size(), first = nf <= (size_t)kColBatch ? nf : kFuseFirst;
+    m.chunk.push_back(0);
+    m.chunk.push_back(first);
+    m.dev_chunk = 1;
+    for (size_t k = first; k < nf;) m.chunk.push_back(k = std::min(nf, k + (size_t)kColFrames));
+}
+
+// Launch k of the call's fused marches on st, into the call's output (march_columns' rule for the upload)
+void march_fused(vr_ctx* c, const ColumnMarches& m, size_t k, float4* out, hipStream_t st) {
+    const VrcFrame* dev = nullptr;
+    if (k >= m.dev_chunk) {
+        dev = c->colframes.as<VrcFrame>() + (m.chunk[k] - m.chunk[m.dev_chunk]);
+        if (st != m.up_st) hip_check(hipStreamWaitEvent(st, m.up_ev, 0));
+    }
+    hip_check(launch_vrc_fused(m.fcs.data() + m.chunk[k], (int)(m.chunk[k + 1] - m.chunk[k]), m.grid,
+                               c->cls_vrc.as<uint8_t>(), c->pmaps.as<int32_t>(), c->tf_rgba.as<float4>(),
+                               (int)c->tf.size(), out, st, c->batch,
+                               (c->leafcols ? c->occ_leafcols : c->occ_cols).as<unsigned long long>(), nullptr, dev));
+}
+
 int vr_render_batch(vr_ctx* c, const vr_params* p, const vr_camera* cams, int32_t n_frames, float* out,
                     int32_t out_flags) {
     if (!c || !cams || n_frames <= 0) return VR_EINVAL;
@@ -2705,7 +2841,27 @@ int vr_render_batch(vr_ctx* c, const vr_params* p, const vr_camera* cams, int32_
             for (int32_t f = 0; f < n_frames; ++f) rects[(size_t)f] = visible_rect(c, p, &cams[f], kWgRaysX, kWgRaysY);
         std::vector<ColumnSlice> pre;
         ColumnMarches m;
-        plan_columns(c, p, cams, n_frames, rects, m, pre);
+        // vr_options.column_fused: the frames it takes (done) are rendered by the fused launches -- on the
+        // caller's stream ahead of the fork (kFuseSched 0), or launch k on in-flight stream k mod ns when the
+        // host reaches the launch's first frame (1) -- with no fork of their own, no join and no event but
+        // the upload's; the frame loop below skips them.  A call with such frames has no column marches.
+        std::vector<char> done;
+        ColumnMarches fm;
+        plan_fused(c, p, cams, n_frames, rects, fm, done);
+        const size_t nfused = fm.fcs.empty() ? 0 : fm.chunk.size() - 1;
+        float4* const out4 = reinterpret_cast<float4*>(out);
+        std::vector<int> fused_of((size_t)n_frames, -1);   // frame -> the fused launch it opens
+        if (nfused) {
+            pre.assign((size_t)n_frames, ColumnSlice{nullptr, 0, 0, 0, 0});
+            if (kFuseSched == 0 || in_flight_streams(c, n_frames) <= 1) {
+                if (fm.dev_chunk < nfused) upload_columns(c, fm, c->stream);
+                for (size_t k = 0; k < nfused; ++k) march_fused(c, fm, k, out4, c->stream);
+            } else {
+                for (size_t k = 0; k < nfused; ++k) fused_of[(size_t)fm.idx[fm.chunk[k]]] = (int)k;
+            }
+        } else {
+            plan_columns(c, p, cams, n_frames, rects, m, pre);
+        }
         // vr_options.column_overlap.  0, or one stream: the upload and every march first, on the ctx
         // stream, then the fork.  1: only the first chunk (kColFirst frames) comes before the fork; chunk
         // k + 1's march is queued when the host reaches chunk k's first frame, ahead of that chunk's
@@ -2731,6 +2887,12 @@ int vr_render_batch(vr_ctx* c, const vr_params* p, const vr_camera* cams, int32_
         }
         auto in_flight = [&](size_t i) { return i % (size_t)ns ? c->aux_stream[i % (size_t)ns - 1] : c->batch_main; };
         frames_in_flight(c, n_frames, [&](int f) {
+            if (fused_of[(size_t)f] >= 0) {
+                const size_t k = (size_t)fused_of[(size_t)f];
+                if (k == fm.dev_chunk) upload_columns(c, fm, in_flight(k));
+                march_fused(c, fm, k, out4, in_flight(k));
+            }
+            if (done[(size_t)f]) return;
             if (chunk_of[(size_t)f] >= 0) {
                 const size_t k = (size_t)chunk_of[(size_t)f];
                 if (k + 1 < nchunk) {
@@ -3006,6 +3168,24 @@ int vr_axis_columns_plan(vr_ctx* c, const vr_params* p, const vr_camera* cam, in
         out[1] = cp.n0;
         out[2] = cp.n1;
         out[3] = (int32_t)std::min<int64_t>(cp.pixels, INT32_MAX);
+        return VR_OK;
+    });
+}
+
+int vr_column_fused_plan(vr_ctx* c, const vr_params* p, const vr_camera* cam, int32_t out[2]) {
+    if (!c || !cam || !out) return VR_EINVAL;
+    return guard([&] {
+        check_params(p);
+        out[0] = out[1] = 0;
+        if (p->mode != VR_MODE_VRC || !c->opt.column_fused || c->timing) return VR_OK;
+        TileRect rect;
+        if (c->cull) rect = visible_rect(c, p, cam, kWgRaysX, kWgRaysY);
+        const VrcFrame f = make_vrc(c, p, cam);
+        const int s = axis_columns_plan(c, p, f, rect).take ? fuse_shape(f) : -1;
+        if (s >= 0) {
+            out[0] = kFuseLadder[s][0];
+            out[1] = kFuseLadder[s][1];
+        }
         return VR_OK;
     });
 }

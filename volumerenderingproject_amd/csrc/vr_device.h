@@ -62,6 +62,16 @@ struct WlCull {
     double rsw, rsh;
 };
 
+// The fused column march (vrc_march_kernel, FUSE): a workgroup owns a tile of P x Q pixels (multiples of
+// 16), marches the leaf columns under it and stores its pixels.  The frame is ntx x nty such tiles, of
+// which [rx0, rx0 + nrx) x [ry0, ry0 + nry) touch the visible rectangle of 16 x 16 work tiles [vtx0,
+// vtx1) x [vty0, vty1) -- the rectangle whose work tiles have slot >= 0 in the two-kernel path's list,
+// up to its occupancy cull -- and come first in block order; every other tile is the background.
+struct FuseTiles {
+    int32_t P, Q, ntx, nty, rx0, ry0, nrx, nry, vtx0, vtx1, vty0, vty1;
+};
+constexpr int kFuseCols = 256;      // leaf columns a tile may march: one per lane
+
 // Per-frame constants of the VRC march, passed by value (kernarg segment -> SGPRs).
 struct VrcFrame {
     // screen / camera (AppData fields, utils.h:36-74; camera after processInput)
@@ -116,7 +126,10 @@ struct VrcFrame {
     // whole frames, general views: the projected dataset box's hull, edge e keeping the pixels with
     // hull[e][0] x + hull[e][1] y <= hull[e][2] (vr_api.cpp hull_edges); 0 edges = no claim
     int32_t n_hull;
-    float hull[kMaxHull][3];
+    union {
+        float hull[kMaxHull][3];
+        FuseTiles fuse;           // the fused column march's frames (axis views: n_hull = 0, no hull)
+    };
     // shading (VR_FLAG_SHADE)
     float ka, kd, ks, shininess;
     int32_t d1i, d2i, d3i;        // dims as int for gradient clamping

@@ -448,7 +448,79 @@ __device__ __forceinline__ const VrcFrame& frame_arg(const VrcFrame& fa) { retur
 __device__ __forceinline__ const VrcFrame& frame_arg(const ColBatch& fa) { return fa.f[blockIdx.y]; }
 __device__ __forceinline__ const VrcFrame& frame_arg(const VrcFrame* __restrict__ fa) { return fa[blockIdx.y]; }
 
-template <bool F2B, bool ESS, bool IDX64, int GEOM, int K, bool SHADE, int STATS = 0, bool COLS = false, bool DEVF = false>
+// The fused column march (vrc_march_kernel, FUSE): the bounding leaf-column rectangle [c0, c0 + n0) x
+// [c1, c1 + n1) of the pixel tile [x0, x0 + P) x [y0, y0 + Q), clipped to the frame, within the frame's
+// own column rectangle.  Why the four corner pixels bound it: a pixel's coordinate on a fixed axis a is
+// q = ((tlc_a + A right_a) + B (-up_a)) + 0.5 with A = (float)x rsw / W and B = (float)y rsh / H
+// (ray_origin, axis_leaf_column), and v = q leaves.  Every one of these float operations is monotone
+// (non-decreasing or non-increasing, by the sign of its constant operand; rounding keeps order), so v is
+// monotone in x for a fixed y and in y for a fixed x, and over a rectangle of pixels it takes its
+// extremes at corners.  j(v) below -- 0 under 0, nleaf - 1 from nleaf on, else (int)v -- is monotone in v
+// and equals axis_leaf_column's index for every pixel inside the cube (0 <= q < 1), the only pixels
+// whose column is ever read (hit, below).  So such a pixel's column lies in [min, max] of the corners'
+// j on either axis: no widening needed.  (axis_leaf_column's own clamp is not monotone outside the
+// cube -- a negative v wraps to nleaf - 1 -- hence j.)  Wave-uniform; the results are made scalar.
+__device__ __forceinline__ void fuse_columns(const VrcFrame& f, int ma, int x0, int y0, int& c0, int& c1, int& n0,
+                                             int& n1) {
+    const int x1 = min(x0 + f.fuse.P, f.W) - 1, y1 = min(y0 + f.fuse.Q, f.H) - 1;
+    int lo0 = f.nleaf, hi0 = -1, lo1 = f.nleaf, hi1 = -1;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float P0[3];
+        ray_origin(f, (k & 1) ? x1 : x0, (k & 2) ? y1 : y0, P0);
+        const float v0 = ((ma == 0 ? P0[1] : P0[0]) + 0.5f) * f.leaves;
+        const float v1 = ((ma == 2 ? P0[1] : P0[2]) + 0.5f) * f.leaves;
+        const int j0 = v0 >= 0.0f ? (v0 < (float)f.nleaf ? (int)v0 : f.nleaf - 1) : 0;
+        const int j1 = v1 >= 0.0f ? (v1 < (float)f.nleaf ? (int)v1 : f.nleaf - 1) : 0;
+        lo0 = min(lo0, j0); hi0 = max(hi0, j0);
+        lo1 = min(lo1, j1); hi1 = max(hi1, j1);
+    }
+    c0 = max(lo0, f.col_i0);
+    c1 = max(lo1, f.col_i1);
+    n0 = max(0, min(hi0, f.col_i0 + f.col_n0 - 1) - c0 + 1);
+    n1 = max(0, min(hi1, f.col_i1 + f.col_n1 - 1) - c1 + 1);
+    c0 = __builtin_amdgcn_readfirstlane(c0); c1 = __builtin_amdgcn_readfirstlane(c1);
+    n0 = __builtin_amdgcn_readfirstlane(n0); n1 = __builtin_amdgcn_readfirstlane(n1);
+}
+
+// The pixel tile of workgroup b of a fused launch: the tiles that touch the visible rectangle first
+// (y fastest), so the marching workgroups are dispatched ahead of the background ones; then the tile
+// columns left of the rectangle, the tiles above and below it, and the columns right of it.  slot: 0 = a
+// tile of the rectangle, -1 = background only.  Wave-uniform.
+__device__ __forceinline__ WorkTile fuse_tile(const FuseTiles& t, int b) {
+    const int n_rect = t.nrx * t.nry;
+    int tx, ty;
+    if (b < n_rect) {
+        tx = t.rx0 + b / t.nry;
+        ty = t.ry0 + b % t.nry;
+    } else {
+        int k = b - n_rect;
+        const int left = t.rx0 * t.nty, gap = t.nty - t.nry;
+        if (k < left) {
+            tx = k / t.nty;
+            ty = k % t.nty;
+        } else if (k < left + t.nrx * gap) {   // (gap > 0 here)
+            k -= left;
+            tx = t.rx0 + k / gap;
+            ty = k % gap;
+            if (ty >= t.ry0) ty += t.nry;
+        } else {
+            k -= left + t.nrx * gap;
+            tx = t.rx0 + t.nrx + k / t.nty;
+            ty = k % t.nty;
+        }
+    }
+    return WorkTile{tx * t.P, ty * t.Q, b < n_rect ? 0 : -1, 0};
+}
+
+__device__ __forceinline__ void expand_pixel(const WorkTile& wt, int& x, int& y);
+__device__ __forceinline__ void expand_store(float4* p, float4 v);
+
+// FUSE (with COLS; the column path's scope): one kernel marches the columns under a tile of pixels and
+// stores the tile -- see FuseTiles (vr_device.h) and the end of the kernel.  f.W x f.H stays the pixel
+// frame, f.col_* the frame's column rectangle, f.col_ofs the frame's first float4 in `out`.
+template <bool F2B, bool ESS, bool IDX64, int GEOM, int K, bool SHADE, int STATS = 0, bool COLS = false, bool DEVF = false,
+          bool FUSE = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves<GEOM, ESS, K, SHADE>()))) void vrc_march_kernel(typename FrameArg<COLS, DEVF>::type fa, const WorkTile* __restrict__ work,
                                                         const int32_t* __restrict__ order,
                                                         const uint8_t* __restrict__ cls,
@@ -497,10 +569,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
     // no work list -- the grid is 8 equal chunks of the rectangle's 16 x 16 tiles in x-major order,
     // chunk blockIdx.x % 8 on its XCD, so each XCD's L2 holds one slab of the class volume
     int b_first = (int)blockIdx.x;
-    if constexpr (COLS) b_first = (b_first & 7) * ((int)gridDim.x >> 3) + (b_first >> 3);
-    const bool b_ok = b_first >= 0 && b_first < f.n_work;
+    if constexpr (COLS && !FUSE) b_first = (b_first & 7) * ((int)gridDim.x >> 3) + (b_first >> 3);
+    const bool b_ok = FUSE || (b_first >= 0 && b_first < f.n_work);
     WorkTile wt_first;
-    if constexpr (COLS) {
+    if constexpr (FUSE) {
+        wt_first = fuse_tile(f.fuse, b_first);   // (one pixel tile per workgroup, no list)
+    } else if constexpr (COLS) {
         const int nty = (f.H + kWgRaysY - 1) / kWgRaysY;
         wt_first = WorkTile{(b_first / nty) * kWgRaysX, (b_first % nty) * kWgRaysY, 0, 0};
     } else {
@@ -512,8 +586,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
     asm volatile("" ::"s"(f.out_tiles), "s"(f.bg_first), "s"(f.n_slots), "s"(f.n_hull), "s"(f.W), "s"(f.H),
                  "s"((uint64_t)gtab_out), "s"((uint64_t)tf_rgba));
     const int ma = AXIS1 ? f.axis1 : 0;
-    float4* s_tf = reinterpret_cast<float4*>(smem);
-    unsigned char* p = smem + (size_t)(n_tf + 1) * sizeof(float4);
+    // FUSE: the tile's marched columns, one float4 per lane, ahead of everything else
+    constexpr size_t kFuseLds = FUSE ? kFuseCols * sizeof(float4) : 0;
+    float4* s_col = reinterpret_cast<float4*>(smem);
+    float4* s_tf = reinterpret_cast<float4*>(smem + kFuseLds);
+    unsigned char* p = smem + kFuseLds + (size_t)(n_tf + 1) * sizeof(float4);
     // general views: each leaf map has f.pad kMapOut entries on either side (s_mx[-pad .. nleaf + pad))
     const int pad = AXIS1 ? 0 : f.pad;
     idx_t* s_mx = reinterpret_cast<idx_t*>(p) + pad;
@@ -558,6 +635,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
         }
         return false;
     };
+    // FUSE: the tile's column rectangle
+    int tc0 = 0, tc1 = 0, tn0 = 0, tn1 = 0;
+    if constexpr (FUSE) fuse_columns(f, ma, wt_first.x0, wt_first.y0, tc0, tc1, tn0, tn1);
     // Per-ray state.  AXIS1: the two fixed axes a0 < a1 are hoisted (q_c = P0_c + 0.5 exactly since
     // front_c == 0; t * 0 adds a signed zero), their leaf -> class-offset maps read from global (L2
     // resident) together with the ray's occupancy column, all in one round of loads.
@@ -570,6 +650,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
     };
     auto init_ray = [&](const WorkTile& wt, Ray& R) {
         ray_of_thread(wt, R.x, R.y);
+        if constexpr (FUSE) {   // lane l's work item: column l of the tile's column rectangle, n1 fastest
+            R.x = (int)threadIdx.x / max(tn1, 1);
+            R.y = (int)threadIdx.x - R.x * tn1;
+        }
         if constexpr (COLS) {
             // a lane's work item is the leaf column (f.col_i0 + x, f.col_i1 + y); the AXIS1 march reads
             // none of the per-pixel geometry (SHADE, which does, has no column march)
@@ -591,8 +675,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
             if constexpr (COLS) {
                 // (every column of the rectangle lies in the cube; the expand pass tests its pixels)
                 const unsigned lim = (unsigned)(f.nleaf - 1);
-                i0 = (int)min((unsigned)(f.col_i0 + R.x), lim);
-                i1 = (int)min((unsigned)(f.col_i1 + R.y), lim);
+                i0 = (int)min((unsigned)((FUSE ? tc0 : f.col_i0) + R.x), lim);
+                i1 = (int)min((unsigned)((FUSE ? tc1 : f.col_i1) + R.y), lim);
             } else {
                 axis_leaf_column(f, ma, R.P0, i0, i1, in_cube);
             }
@@ -609,6 +693,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
             // blend): no batch at all, instead of one batch of no-ops after the first empty-cell jump
             if (ESS && R.colmask == 0ull && f.zero_transparent) R.s_end = 0;
         }
+        if (FUSE && (int)threadIdx.x >= tn0 * tn1) R.s_end = 0;   // a lane without a column: an empty range
     };
     Ray R;
     // the TF entries join the first round of staging loads (n_tf <= kMaxTf = kWgThreads, host)
@@ -653,7 +738,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
 #ifndef VR_VRC_LOCK
 #define VR_VRC_LOCK 0
 #endif
-    constexpr bool LOCKV = VR_VRC_LOCK && SPLIT && !IDX64 && F2B && !SHADE && ESS && STATS != 1;
+    constexpr bool LOCKV = VR_VRC_LOCK && SPLIT && !IDX64 && F2B && !SHADE && ESS && STATS != 1 && !FUSE;
     // (the wave reads the published view table through scalar loads: no LDS copy of it)
     const bool lock_run = LOCKV && f.zero_transparent && f.cls0 == 0;
     const bool lock_scalar = lock_run && gtab != nullptr;
@@ -676,7 +761,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
             v4[u] = make_int4((int)w[0], (int)w[1], (int)w[2], (int)w[3]);
         }
     }
-    if ((f.out_tiles == 0) & ((int)blockIdx.x >= f.bg_first)) {
+    if constexpr (FUSE) {
+        // a tile off the visible rectangle: exactly the background.  Workgroup-uniform, ahead of every
+        // barrier and of the waits for the staging loads above
+        if (wt_first.slot < 0) {
+            const float4 bg = make_float4(f.bg[0], f.bg[1], f.bg[2], 1.0f);
+            for (int sx = 0; sx < f.fuse.P; sx += kWgRaysX)
+                for (int sy = 0; sy < f.fuse.Q; sy += kWgRaysY) {
+                    int x, y;
+                    expand_pixel(WorkTile{wt_first.x0 + sx, wt_first.y0 + sy, 0, 0}, x, y);
+                    if (x < f.W && y < f.H) expand_store(out + (int64_t)x * f.H + y, bg);
+                }
+            return;
+        }
+    }
+    if (!FUSE && ((f.out_tiles == 0) & ((int)blockIdx.x >= f.bg_first))) {
         // a background-only workgroup: bg_group culled work tiles off the projected dataset box,
         // each exactly the background (no staging, no march)
         const int e0 = f.bg_first + ((int)blockIdx.x - f.bg_first) * f.bg_group;
@@ -713,7 +812,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
         }
     }
     if (AXIS1) {
-        if (culled_exit()) return;
+        if (!FUSE && culled_exit()) return;
         init_ray(wt_first, R);   // the ray's map / column loads: issued before the staging stores wait
         if (!lock_scalar) {
 #pragma unroll
@@ -795,18 +894,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
 
     // Persistent when gridDim < n_slots: a workgroup walks slots blockIdx.x, +gridDim.x, ... (gridDim
     // is a multiple of 8, so a workgroup stays on the XCD band its first slot belongs to).
-    for (int blk = blockIdx.x; blk < f.n_slots; blk += gridDim.x) {
+    // FUSE: exactly one pass, and none of its lanes leaves it early -- every lane of a marching workgroup
+    // reaches the barrier behind it (a lane with nothing to march has the empty range s_end = 0)
+    for (int blk = blockIdx.x; blk < (FUSE ? (int)blockIdx.x + 1 : f.n_slots); blk += FUSE ? 1u : (unsigned)gridDim.x) {
     unsigned long long t_start = 0;
     if (STATS == 1) t_start = __builtin_amdgcn_s_memrealtime();
     const bool first = blk == (int)blockIdx.x;
     const int b = first ? b_first : blk;
-    if (b < 0 || b >= f.n_work) continue;
+    if (!FUSE && (b < 0 || b >= f.n_work)) continue;
     const WorkTile wt = (first || COLS) ? wt_first : work[b];   // (COLS: one tile per workgroup)
     if (!first) init_ray(wt, R);
     const int x = R.x, y = R.y;
-    const bool lane_ok = x < f.W && y < f.H;
+    const bool lane_ok = FUSE || (x < f.W && y < f.H);
     if (!lock_run && !lane_ok) continue;   // (lockstep: every lane takes part in the wave's reductions)
-    if (!f.out_tiles && wt.slot < 0) {   // culled tile (persistent grids reach them here)
+    if (!FUSE && !f.out_tiles && wt.slot < 0) {   // culled tile (persistent grids reach them here)
         if (lane_ok) store_f4(out + (int64_t)x * f.H + y, make_float4(f.bg[0], f.bg[1], f.bg[2], 1.0f));
         continue;
     }
@@ -1490,7 +1591,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
         if (F2B ? (s >= s_end) : (s < s_begin)) done = true;
     }
     if (F2B) { r = r + T * f.bg[0]; g = g + T * f.bg[1]; bl = bl + T * f.bg[2]; }
-    store_pixel(out, out_index(f.out_tiles, wt, x, y, f.H, f.tile_w, f.tile_h), f.out_rgb, r, g, bl);
+    if constexpr (FUSE) s_col[threadIdx.x] = make_float4(r, g, bl, 1.0f);   // what the column march stores
+    else store_pixel(out, out_index(f.out_tiles, wt, x, y, f.H, f.tile_w, f.tile_h), f.out_rgb, r, g, bl);
     // counting pass (vr_count_work): class gathers that touched memory, their bytes and the samples
     // evaluated (batches x K) of this ray, summed over the frame
     if (STATS == 2) count_work(stats, st_loads, st_bytes, st_iter * K);
@@ -1509,6 +1611,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
         ls[1] = (unsigned long long)st_jumps | (1ull << 63);
     }
     }   // slot loop
+    if constexpr (FUSE) {
+        // The tile's pixels, with the expand pass's per-pixel code: 16 x 16 pixels at a time in its 8 x 8-
+        // per-wave mapping (128-byte segments), the pixel's column from ray_origin and axis_leaf_column,
+        // its hit test -- `vis`, the pixel's 16 x 16 work tile lies in the visible rectangle, standing for
+        // the list's slot >= 0 (a work tile that list culls for its empty cell columns is marched here:
+        // empty columns are exactly the background) -- and then the column from LDS or the background.
+        // (t0 < tn0, t1 < tn1 follow from the other terms, fuse_columns; they keep the LDS index in range.)
+        __syncthreads();
+        const float4 bg = make_float4(f.bg[0], f.bg[1], f.bg[2], 1.0f);
+        const unsigned vnx = (unsigned)(f.fuse.vtx1 - f.fuse.vtx0), vny = (unsigned)(f.fuse.vty1 - f.fuse.vty0);
+        for (int sx = 0; sx < f.fuse.P; sx += kWgRaysX)
+            for (int sy = 0; sy < f.fuse.Q; sy += kWgRaysY) {
+                int x, y;
+                expand_pixel(WorkTile{wt_first.x0 + sx, wt_first.y0 + sy, 0, 0}, x, y);
+                float P0[3];
+                int i0, i1;
+                bool in_cube;
+                ray_origin(f, x, y, P0);
+                axis_leaf_column(f, ma, P0, i0, i1, in_cube);
+                const unsigned c0 = (unsigned)(i0 - f.col_i0), c1 = (unsigned)(i1 - f.col_i1);
+                const unsigned t0 = (unsigned)(i0 - tc0), t1 = (unsigned)(i1 - tc1);
+                const bool vis = ((unsigned)((x >> 4) - f.fuse.vtx0) < vnx) & ((unsigned)((y >> 4) - f.fuse.vty0) < vny);
+                const bool hit = (x < f.W) & (y < f.H) & vis & in_cube & (c0 < (unsigned)f.col_n0) &
+                                 (c1 < (unsigned)f.col_n1) & (t0 < (unsigned)tn0) & (t1 < (unsigned)tn1);
+                const float4 v = s_col[hit ? t0 * (unsigned)tn1 + t1 : 0u];
+                if (x < f.W && y < f.H) expand_store(out + (int64_t)x * f.H + y, hit ? v : bg);
+            }
+    }
 }
 
 // must match the kernel's LDS carve-up (vrc_march_kernel prologue)
@@ -1553,7 +1683,7 @@ size_t vrc_axis1_table_bytes(const VrcFrame& f, int batch) {
     return (n_tab * (f.tsplit ? 8 : 4) + (size_t)f.ncell * 4 + n_tab + 3) & ~(size_t)3;
 }
 
-template <int STATS, int K, bool COLS = false, bool DEVF = false>
+template <int STATS, int K, bool COLS = false, bool DEVF = false, bool FUSE = false>
 static void launch_vrc_variant(const VrcFrame& f, const WorkTile* work, const int32_t* order, int n_blocks_in,
                                const uint8_t* cls, const int32_t* maps, const int64_t* mapx64, const uint32_t* occ,
                                const float4* tf, int n_tf, float4* out, unsigned long long* stats, hipStream_t st,
@@ -1563,7 +1693,7 @@ static void launch_vrc_variant(const VrcFrame& f, const WorkTile* work, const in
     const bool f2b = (f.flags & 2) != 0, ess = (f.flags & 1) != 0 && f.zero_transparent;
     const bool shade = (f.flags & 8) != 0;
     const bool idx64 = mapx64 != nullptr, ax1 = f.axis1 >= 0;
-    const size_t lds = vrc_lds_bytes(f, n_tf, idx64, K);
+    const size_t lds = vrc_lds_bytes(f, n_tf, idx64, K) + (FUSE ? kFuseCols * sizeof(float4) : 0);
     // f.persist_wgs > 0: persistent grid of 256 CUs x persist_wgs workgroups (multiple of 8)
     int n_blocks = n_blocks_in;
     if (f.persist_wgs > 0) n_blocks = std::min(n_blocks_in, 256 * f.persist_wgs);
@@ -1579,7 +1709,7 @@ static void launch_vrc_variant(const VrcFrame& f, const WorkTile* work, const in
         fa = f;
     }
 #define VR_L(F2B_, ESS_, I64_, AX_, SH_)                                                                    \
-    hipLaunchKernelGGL((vrc_march_kernel<F2B_, ESS_, I64_, AX_, K, SH_, STATS, COLS, DEVF>), dim3(n_blocks, n_frames), dim3(kWgThreads), \
+    hipLaunchKernelGGL((vrc_march_kernel<F2B_, ESS_, I64_, AX_, K, SH_, STATS, COLS, DEVF, FUSE>), dim3(n_blocks, n_frames), dim3(kWgThreads), \
                        lds, st, fa, work, order, cls, maps, mapx64, occ, tf, n_tf, out, stats, vol, rawmaps, occcol, cdist, gtab, gtab_out)
 #define VR_L2(I64_, AX_, SH_)                                                                            \
     if (f2b) { if (ess) VR_L(true, true, I64_, AX_, SH_); else VR_L(true, false, I64_, AX_, SH_); } \
@@ -2187,6 +2317,44 @@ hipError_t launch_vrc_columns(const VrcFrame* fs, int n_frames, int n_blocks, co
         launch_vrc_variant<0, 8, true>(f, nullptr, nullptr, n_blocks, cls, maps, nullptr, nullptr, tf, n_tf, colbuf,
                                        nullptr, st, nullptr, nullptr, occcol, nullptr, gtab, gtab_out, colframes,
                                        n_frames);
+    return hipGetLastError();
+}
+
+// The fused column march of the n_frames frames fs[] in one launch (grid y): frame f's pixel tiles (f.fuse)
+// marched and stored into out + f.col_ofs.  Every frame of a launch has the same size and tile shape, so
+// n_blocks = their common tile count (checked).  Kernel variant, LDS size and dev_frames as for
+// launch_vrc_columns.
+hipError_t launch_vrc_fused(const VrcFrame* fs, int n_frames, int n_blocks, const uint8_t* cls, const int32_t* maps,
+                            const float4* tf, int n_tf, float4* out, hipStream_t st, int batch,
+                            const unsigned long long* occcol, const int32_t* gtab, const VrcFrame* dev_frames) {
+    if (n_frames < 1 || n_frames > (dev_frames ? kColFrames : kColBatch)) return hipErrorInvalidValue;
+    const VrcFrame& f = fs[0];
+    for (int i = 0; i < n_frames; ++i) {
+        const FuseTiles& t = fs[i].fuse;
+        if (t.P < kWgRaysX || t.Q < kWgRaysY || t.P % kWgRaysX || t.Q % kWgRaysY || t.ntx * t.nty != n_blocks ||
+            t.ntx != (fs[i].W + t.P - 1) / t.P || t.nty != (fs[i].H + t.Q - 1) / t.Q || t.rx0 < 0 || t.ry0 < 0 ||
+            t.nrx < 0 || t.nry < 0 || t.rx0 + t.nrx > t.ntx || t.ry0 + t.nry > t.nty)
+            return hipErrorInvalidValue;
+    }
+    if (dev_frames) {
+        if (vrc_batch(f, batch) == 16)
+            launch_vrc_variant<0, 16, true, true, true>(f, nullptr, nullptr, n_blocks, cls, maps, nullptr, nullptr, tf,
+                                                        n_tf, out, nullptr, st, nullptr, nullptr, occcol, nullptr, gtab,
+                                                        nullptr, dev_frames, n_frames);
+        else
+            launch_vrc_variant<0, 8, true, true, true>(f, nullptr, nullptr, n_blocks, cls, maps, nullptr, nullptr, tf,
+                                                       n_tf, out, nullptr, st, nullptr, nullptr, occcol, nullptr, gtab,
+                                                       nullptr, dev_frames, n_frames);
+        return hipGetLastError();
+    }
+    if (vrc_batch(f, batch) == 16)
+        launch_vrc_variant<0, 16, true, false, true>(f, nullptr, nullptr, n_blocks, cls, maps, nullptr, nullptr, tf, n_tf,
+                                                     out, nullptr, st, nullptr, nullptr, occcol, nullptr, gtab, nullptr,
+                                                     fs, n_frames);
+    else
+        launch_vrc_variant<0, 8, true, false, true>(f, nullptr, nullptr, n_blocks, cls, maps, nullptr, nullptr, tf, n_tf,
+                                                    out, nullptr, st, nullptr, nullptr, occcol, nullptr, gtab, nullptr,
+                                                    fs, n_frames);
     return hipGetLastError();
 }
 

@@ -50,7 +50,7 @@ EXPORTED = [
     "vr_assemble_tile_slots_multi", "vr_options_default", "vr_create_ex", "vr_get_options", "vr_set_options",
     "vr_create_multi", "vr_comm_unique_id", "vr_create_rank", "vr_group_info", "vr_group_tiles", "vr_render_png",
     "vr_render_batch", "vr_create_multi_ex", "vr_group_timing_read", "vr_count_work", "vr_group_traffic_read",
-    "vr_axis_columns_plan", "vr_tf_segments", "vr_set_isosurface", "vr_get_isosurface",
+    "vr_axis_columns_plan", "vr_column_fused_plan", "vr_tf_segments", "vr_set_isosurface", "vr_get_isosurface",
     "vr_set_colormap", "vr_get_colormap", "vr_colormap_eval",
     "vr_set_gradient_opacity", "vr_get_gradient_opacity", "vr_gradient_opacity_eval",
     "vr_set_crop_box", "vr_get_crop_box",
@@ -135,7 +135,8 @@ class Options(C.Structure):
                 ("leaf_columns", C.c_int32),
                 ("axis_columns", C.c_int32),
                 ("dvr_volume", C.c_int32),
-                ("column_overlap", C.c_int32)]
+                ("column_overlap", C.c_int32),
+                ("column_fused", C.c_int32)]
 
 
 class WorkCount(C.Structure):
@@ -209,6 +210,7 @@ def lib():
         "vr_count_marched": ([vp, P(RenderParams), P(Camera), P(C.c_uint64), P(C.c_uint64)], C.c_int),
         "vr_count_work": ([vp, P(RenderParams), P(Camera), P(WorkCount)], C.c_int),
         "vr_axis_columns_plan": ([vp, P(RenderParams), P(Camera), P(C.c_int32)], C.c_int),
+        "vr_column_fused_plan": ([vp, P(RenderParams), P(Camera), P(C.c_int32)], C.c_int),
         "vr_tf_segments": ([P(TFInterval), C.c_int32, C.c_double, P(C.c_float), P(C.c_int32), C.c_int32,
                             P(C.c_int32)], C.c_int),
         "vr_synchronize": ([vp], C.c_int),
@@ -715,6 +717,13 @@ class VolumeRenderer:
         o = (C.c_int32 * 4)()
         _check(lib().vr_axis_columns_plan(self._ctx, C.byref(params), C.byref(camera), o), "vr_axis_columns_plan")
         return {"columns": bool(o[0]), "n0": int(o[1]), "n1": int(o[2]), "pixels": int(o[3])}
+
+    def column_fused_plan(self, params, camera):
+        """(P, Q): the pixel tile of a workgroup if vr_render renders this frame with the fused column
+        march (vr_options.column_fused), else None (vr_column_fused_plan: decided on the host)."""
+        o = (C.c_int32 * 2)()
+        _check(lib().vr_column_fused_plan(self._ctx, C.byref(params), C.byref(camera), o), "vr_column_fused_plan")
+        return (int(o[0]), int(o[1])) if o[0] else None
 
     def synchronize(self):
         _check(lib().vr_synchronize(self._ctx), "vr_synchronize")
