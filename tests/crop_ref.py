@@ -15,6 +15,10 @@ Built from the six modes' restatements by composition (imported, not copied; non
                and the light read the whole volume
 
 box = (lo, hi), or None for the box off (the mode's own restatement).
+
+Each function takes what does not depend on the box ready-made (colors / samples: the mode's per-sample
+colours or values, P: the frame's positions), so that the samples of one frame are evaluated once for all
+its boxes (tests/crop_cases.py); the frames are the same bit for bit either way.
 """
 import numpy as np
 
@@ -41,9 +45,11 @@ def points_in_box(P, box):
                 (P[2] >= lo[2]) & (P[2] < hi[2]))
 
 
-def in_box(shape, p, cam, box, xs=None):
-    """The in-box mask of every sample of the frame, bool [nx, H, S] (all True with the box off)."""
-    P = dvr_ref.positions(shape, p, cam, xs)
+def in_box(shape, p, cam, box, xs=None, P=None):
+    """The in-box mask of every sample of the frame, bool [nx, H, S] (all True with the box off).  P: the
+    frame's dvr_ref.positions, to share them among the boxes of one frame."""
+    if P is None:
+        P = dvr_ref.positions(shape, p, cam, xs)
     if box is None:
         return np.ones(P[0].shape, bool)
     return points_in_box(P, box)
@@ -64,42 +70,46 @@ def cmap_outside(points):
     return cmap_ref.C(points, np.zeros(1, F))[0]
 
 
-def dvr(vol, cal_max, tf, p, cam, box, xs=None):
-    """The VR_MODE_DVR frame under the box, float32 [nx, H, 4]."""
-    col = dvr_ref.sample_colors(vol, cal_max, tf, p, cam, xs)
-    col = _replace(col, in_box(np.shape(vol), p, cam, box, xs), tf_outside(cal_max, tf))
+def dvr(vol, cal_max, tf, p, cam, box, xs=None, colors=None, P=None):
+    """The VR_MODE_DVR frame under the box, float32 [nx, H, 4] (colors: dvr_ref.sample_colors' result, to
+    share one frame's samples among its boxes)."""
+    col = dvr_ref.sample_colors(vol, cal_max, tf, p, cam, xs) if colors is None else colors
+    col = _replace(col, in_box(np.shape(vol), p, cam, box, xs, P), tf_outside(cal_max, tf))
     return cmap_ref.blend(col, p)   # (dvr_ref.render's blend, as a function of the colours)
 
 
-def sdvr(vol, cal_max, tf, p, cam, shade, box, xs=None):
-    """(frame, lit bool [nx, H, S]): VR_MODE_SDVR under the box and its shaded samples."""
-    col, rec = sdvr_ref.shade_samples(vol, cal_max, tf, p, cam, shade, xs)
-    keep = in_box(np.shape(vol), p, cam, box, xs)
+def sdvr(vol, cal_max, tf, p, cam, shade, box, xs=None, colors=None, P=None):
+    """(frame, lit bool [nx, H, S]): VR_MODE_SDVR under the box and its shaded samples (colors:
+    sdvr_ref.shade_samples' (col, record), to share one frame's samples among its boxes)."""
+    col, rec = sdvr_ref.shade_samples(vol, cal_max, tf, p, cam, shade, xs) if colors is None else colors
+    keep = in_box(np.shape(vol), p, cam, box, xs, P)
     col = _replace(col, keep, tf_outside(cal_max, tf))
     with np.errstate(over="ignore", invalid="ignore"):
         return cmap_ref.blend(col, p), rec["shaded"] & keep
 
 
-def cdvr(vol, points, p, cam, box, xs=None, samples=None):
-    """The VR_MODE_CDVR frame under the box."""
-    col = cmap_ref.sample_colors(vol, points, p, cam, xs, samples)
-    col = _replace(col, in_box(np.shape(vol), p, cam, box, xs), cmap_outside(points))
+def cdvr(vol, points, p, cam, box, xs=None, samples=None, colors=None, P=None):
+    """The VR_MODE_CDVR frame under the box (colors: cmap_ref.sample_colors' result under these points)."""
+    col = cmap_ref.sample_colors(vol, points, p, cam, xs, samples) if colors is None else colors
+    col = _replace(col, in_box(np.shape(vol), p, cam, box, xs, P), cmap_outside(points))
     return cmap_ref.blend(col, p)
 
 
-def scdvr(vol, points, gopa, p, cam, shade, box, xs=None, samples=None):
-    """(frame, lit bool [nx, H, S]): VR_MODE_SCDVR under the box and its lit samples."""
-    col, rec = scdvr_ref.lit_samples(vol, points, gopa, p, cam, shade, xs, samples)
-    keep = in_box(np.shape(vol), p, cam, box, xs)
+def scdvr(vol, points, gopa, p, cam, shade, box, xs=None, samples=None, colors=None, P=None):
+    """(frame, lit bool [nx, H, S]): VR_MODE_SCDVR under the box and its lit samples (colors:
+    scdvr_ref.lit_samples' (col, record) under these ingredients)."""
+    col, rec = scdvr_ref.lit_samples(vol, points, gopa, p, cam, shade, xs, samples) if colors is None else colors
+    keep = in_box(np.shape(vol), p, cam, box, xs, P)
     col = _replace(col, keep, cmap_outside(points))
     with np.errstate(over="ignore", invalid="ignore"):
         return cmap_ref.blend(col, p), rec["lit"] & keep
 
 
-def mip(vol, cal_max, p, cam, box, xs=None):
-    """(frame, hit bool [nx, H]): VR_MODE_MIP under the box -- mip_ref.render with inside &= in_box."""
-    v, inside = mip_ref.sample_values(vol, p, cam, xs)
-    inside = inside & in_box(np.shape(vol), p, cam, box, xs)
+def mip(vol, cal_max, p, cam, box, xs=None, samples=None, P=None):
+    """(frame, hit bool [nx, H]): VR_MODE_MIP under the box -- mip_ref.render with inside &= in_box
+    (samples: mip_ref.sample_values' (v, inside))."""
+    v, inside = mip_ref.sample_values(vol, p, cam, xs) if samples is None else samples
+    inside = inside & in_box(np.shape(vol), p, cam, box, xs, P)
     m = np.full(v.shape[:2], -np.inf, F)
     for s in range(v.shape[2]):
         take = inside[:, :, s] & (v[:, :, s] > m)
@@ -115,16 +125,17 @@ def mip(vol, cal_max, p, cam, box, xs=None):
     return f, hit
 
 
-def iso(vol, p, cam, iso_value, rgb, shade, box, xs=None):
+def iso(vol, p, cam, iso_value, rgb, shade, box, xs=None, samples=None, P=None):
     """(frame, record {hit, s_h, refinable}): VR_MODE_ISO under the box -- iso_ref.render's steps, the box in
-    the hit test, in the test of sample s_h - 1 and in the test of every bisection midpoint."""
+    the hit test, in the test of sample s_h - 1 and in the test of every bisection midpoint (samples:
+    mip_ref.sample_values' (v, inside))."""
     vol = np.ascontiguousarray(vol, F)
     dims = vol.shape
     iso_value = F(iso_value)
     ka, kd, ks, shin = (F(c) for c in shade)
     S = p.samples_per_ray
-    v, inside = mip_ref.sample_values(vol, p, cam, xs)
-    inside = inside & in_box(dims, p, cam, box, xs)
+    v, inside = mip_ref.sample_values(vol, p, cam, xs) if samples is None else samples
+    inside = inside & in_box(dims, p, cam, box, xs, P)
     with np.errstate(invalid="ignore"):
         ge = inside & (v >= iso_value)
     hit = ge.any(axis=2)

@@ -73,29 +73,83 @@ def _ray_positions(shape, p, cam, x, y):
     return [c[0, y, :] for c in P]
 
 
-def box_of(name, shape, p, cam):
+def _in_volume(P, shape, margin=(0.0, 0.0, 0.0)):
+    ok = np.ones(P[0].shape, bool)
+    for a in range(3):
+        ok &= (P[a] >= margin[a]) & (P[a] < shape[a] - margin[a])
+    return ok
+
+
+def box_of(name, shape, p, cam, where=None, axis=2):
     """The named box for a frame: the fixed ones, and the two taken from the frame's own samples.
     slab   a z range thinner than one sample step, around the z of a sample of the centre ray in the volume
+           (10 voxels from its z faces, a quarter of the depth where the volume is shallower); the other two
+           axes reach past the volume.  axis: the slab's axis where it is not z
     faces  lo and hi are the positions of two samples, a third and two thirds of the way along the rays of
-           the pixels a quarter and three quarters into the frame (sorted per axis)"""
+           the pixels a quarter and three quarters into the frame (sorted per axis)
+    where (bool [W, H, S]; the frames off the default parameters, tests/crop_cases.py): the samples the boxes
+    are taken from -- those of the frame that lie in the volume and show.  slab takes the middle one of the
+    centre ray's, away from the z faces as above; failing that the middle one of the whole frame's, away from
+    the faces and then anywhere; and the volume's middle z when `where` is empty.  faces takes the pixels a
+    quarter and three quarters into the bounding rectangle of the rays with such samples, and on the two rays
+    the sample a third and two thirds of the way along their run of them.  An axis on which the two positions
+    coincide (a single sample per ray, a zero viewplane distance) is widened by a quarter voxel either side."""
     if name in AVG_BOXES:
         return AVG_BOXES[name]
     W, H, S = p.width, p.height, p.samples_per_ray
     if name == "slab":
+        def slab(z, half):
+            lo, hi = [-5.0] * 3, [max(200.0, d + 5.0) for d in shape]
+            lo[axis], hi[axis] = z - half, z + half
+            return (tuple(lo), tuple(hi))
+
         P = _ray_positions(shape, p, cam, W // 2, H // 2)
-        ok = np.nonzero((P[0] >= 0) & (P[0] < shape[0]) & (P[1] >= 0) & (P[1] < shape[1]) & (P[2] >= 10) &
-                        (P[2] < shape[2] - 10))[0]
+        m = [0.0, 0.0, 0.0]
+        m[axis] = min(10.0, shape[axis] / 4.0)
+        ok = _in_volume(P, shape, m)
+        if where is not None:
+            ok = np.nonzero(ok & where[W // 2, H // 2])[0]
+            Q = dvr_ref.positions(shape, p, cam)
+            for margin in (m, (0.0, 0.0, 0.0)):
+                if len(ok):
+                    break
+                ix, iy, js = np.nonzero(_in_volume(Q, shape, margin) & where)
+                if len(js):
+                    j = len(js) // 2
+                    P, ok = [c[ix[j], iy[j], :] for c in Q], js[j:j + 1]
+            if len(ok) == 0:
+                return slab(shape[axis] / 2.0, 0.25)
+        else:
+            ok = np.nonzero(ok)[0]
         s = int(ok[len(ok) // 2])
-        z = float(P[2][s])
-        step = abs(float(P[2][min(s + 1, S - 1)]) - float(P[2][max(s - 1, 0)])) / 2.0
+        z = float(P[axis][s])
+        step = abs(float(P[axis][min(s + 1, S - 1)]) - float(P[axis][max(s - 1, 0)])) / 2.0
         half = 0.2 * step if step > 0 else 0.25      # (a view along which z does not move: a quarter voxel)
-        return ((-5.0, -5.0, z - half), (200.0, 200.0, z + half))
+        return slab(z, half)
     if name == "faces":
-        A = _ray_positions(shape, p, cam, W // 4, H // 4)
-        B = _ray_positions(shape, p, cam, (3 * W) // 4, (3 * H) // 4)
-        a = [float(c[S // 3]) for c in A]
-        b = [float(c[(2 * S) // 3]) for c in B]
-        return (tuple(min(u, v) for u, v in zip(a, b)), tuple(max(u, v) for u, v in zip(a, b)))
+        xa, ya, xb, yb = W // 4, H // 4, (3 * W) // 4, (3 * H) // 4
+        sa, sb = S // 3, (2 * S) // 3
+        if where is not None and where.any():
+            met = where.any(axis=2)
+            xs, ys = np.nonzero(met.any(axis=1))[0], np.nonzero(met.any(axis=0))[0]
+            x0, x1, y0, y1 = int(xs[0]), int(xs[-1]) + 1, int(ys[0]), int(ys[-1]) + 1
+            xa, ya = x0 + (x1 - x0) // 4, y0 + (y1 - y0) // 4
+            xb, yb = x0 + (3 * (x1 - x0)) // 4, y0 + (3 * (y1 - y0)) // 4
+            ia, ib = np.nonzero(where[xa, ya])[0], np.nonzero(where[xb, yb])[0]
+            if len(ia):
+                sa = int(ia[len(ia) // 3])
+            if len(ib):
+                sb = int(ib[(2 * len(ib)) // 3])
+        A = _ray_positions(shape, p, cam, xa, ya)
+        B = _ray_positions(shape, p, cam, xb, yb)
+        a = [float(c[sa]) for c in A]
+        b = [float(c[sb]) for c in B]
+        lo, hi = [min(u, v) for u, v in zip(a, b)], [max(u, v) for u, v in zip(a, b)]
+        if where is not None:
+            for c in range(3):
+                if lo[c] == hi[c]:
+                    lo[c], hi[c] = lo[c] - 0.25, hi[c] + 0.25
+        return (tuple(lo), tuple(hi))
     raise KeyError(name)
 
 

@@ -5,7 +5,8 @@ back-to-front blend, kernel.cu:194-225); ESS + ERT and ERT alone within 1e-4; TE
 (kernel.cu:72-187).  Covers the general-view paths (padded leaf maps, lazy empty-space tests,
 empty-cell skipping of exact frames) on views no other test picks.  The same views in DVR, MIP and ISO
 against tests/dvr_ref.py, mip_ref.py and iso_ref.py (test_random_views_field_modes), and in SDVR, CDVR and
-SCDVR against tests/sdvr_ref.py, cmap_ref.py and scdvr_ref.py (test_random_views_lit_field_modes)."""
+SCDVR against tests/sdvr_ref.py, cmap_ref.py and scdvr_ref.py (test_random_views_lit_field_modes), and in all
+six field modes under a seeded crop box per view against tests/crop_ref.py (test_random_views_crop)."""
 import math
 
 import numpy as np
@@ -156,3 +157,43 @@ def test_random_views_lit_field_modes(seed):
                         assert np.all(got[..., 3] == 1.0)
                     frames += 4
     print("random views, lit field modes: seed", seed, "frames compared", frames, "largest ERT error", worst)
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_random_views_crop(seed):
+    """The same views under a crop box each (crop_cases.random_boxes: per axis whole with probability 1/4,
+    otherwise lo < hi uniform in [-2, d + 2] at least 3 voxels apart), in the six field modes against
+    tests/crop_ref.py, one evaluation of a view's samples shared by the modes.  The rule is
+    test_gpu_crop.check_all_flags: exact and ESS bitwise, MIP and ISO bitwise in all four flag combinations, ERT
+    and ESS | ERT within field_param_cases.random_ert_bound(S); on the byte-copy context for every view and on
+    the float-volume one for every third.  At least half of a seed's views draw under their box."""
+    import crop_cases as cx
+    import field_param_cases as fp
+    import sdvr_cases as sc
+    import test_crop_ref as tc
+    from test_gpu_crop import check_all_flags, set_box
+    vol, cal = sc.volume("avg152")
+    seen, frames, drawing = [], 0, 0
+    boxes = cx.random_boxes(seed, vol.shape)
+    with vr.VolumeRenderer(vol, cal, device=0) as a, \
+            vr.VolumeRenderer(vol, cal, device=0, options=vr.default_options(dvr_volume=1)) as b:
+        for r in (a, b):
+            for mode in ("dvr", "scdvr"):
+                cx.apply_set(r, mode, 0, "avg152")
+            r.set_isosurface(tc.ISO_VALUE, cx.ISO_RGB)
+        for i, (view, bx) in enumerate(zip(fp.random_view_cases(seed), boxes)):
+            refs, caught = cx.random_references(view, bx)
+            drew = bool(fp.drawn(refs["dvr"], view.bg).any())
+            assert caught > 0 or not drew
+            drawing += drew
+            bound = fp.random_ert_bound(view.S)
+            cam = view.gpu_camera()
+            for r in ((a, b) if i % 3 == 0 else (a,)):
+                set_box(r, bx)
+                for mode in cx.MODES:
+                    check_all_flags(r, mode, refs[mode], view.W, view.H, view.S, cam, (seed, i, mode, bx), bound,
+                                    make=lambda fl: cx.gpu_params(mode, 0, view, fl), seen=seen)
+                    frames += 4
+    print("random views under a crop box: seed", seed, "frames compared", frames, "views drawing", drawing,
+          "largest ERT error", max(seen))
+    assert 2 * drawing >= len(boxes), (seed, drawing)
