@@ -241,6 +241,37 @@ extern "C" {
 #define VR_FLAG_CONIC 16   /* perspective rays: dir = normalize(screen point - camera pos), sample
                               = pos + (s*sd + fc)*dir (kernel.cu:30-34, :53-54; the reference ships
                               it disabled, utils.h:28).  Use vr_camera_derive_conic's top_left.  */
+#define VR_FLAG_PERSP 32   /* the six field modes only */
+/* VR_FLAG_PERSP: perspective rays for VR_MODE_DVR, MIP, ISO, SDVR, CDVR and SCDVR.  With mc, iv, tv the
+ * matrices of VR_MODE_TEST's position chain (modelCam, inverse(lookAt(pos, 0, up)), toVolume; indexed
+ * column-major), all arithmetic float32, every operation rounded on its own, no contraction:
+ *   per frame   rS  = 1.0f / (float)S
+ *   per ray     ax  = mc[0]*(float)x + mc[12]
+ *               ay  = mc[5]*(float)y + mc[13]
+ *               A_r = iv[r]*ax + iv[4+r]*ay                 r = 0, 1, 2
+ *   per sample, at the float sample coordinate fs:
+ *               t   = fs * rS
+ *               qz  = mc[10]*fs + mc[14]
+ *               B_r = iv[8+r]*qz + iv[12+r]*1.0f
+ *               q_r = A_r*t + B_r
+ *               p_r = tv[5r]*q_r + tv[12+r]
+ * -- the orthographic chain's separable form (q_r = A_r + B_r) with A_r scaled by t.  Only these entries
+ * of mc and tv are read (the others are zeros by construction); a non-finite entry gives NaN positions,
+ * samples outside the volume.  The eye is p(x, y, 0), one point for every ray; the frustum's cross-section
+ * at fs = S is the orthographic screen real_screen_width x real_screen_height, so the horizontal field of
+ * view is 2 atan(rsw / (2 viewplane_distance)) (vr_persp_screen).  Of vr_camera only pos and up enter
+ * (through lookAt), as in the orthographic field modes.  The ray of pixel (W/2, H/2) (even W, H) has
+ * ax = ay = +-0: its positions are the orthographic ray's bit for bit.
+ * With the flag, "the positions p(x, y, s)" in each mode's definition reads this law at every place it
+ * occurs -- the march at fs = (float)s, ISO's bisection at fractional fs and its surface point, the
+ * gradient taps' base position (SDVR, SCDVR, ISO), the headlight e = p(S > 1 ? S - 1 : 0) - p(0), now a
+ * direction per ray (a point light at the eye), and the crop-box test -- and nothing else changes:
+ * VR_FLAG_ESS stays bitwise the exact frame, MIP's and ISO's four flag combinations stay bitwise equal,
+ * VR_FLAG_ERT is as in each mode.  The culls are conservative: they make a claim only when every corner
+ * of the dataset box (or the effective crop box) lies at or beyond sample 1 in front of the eye, and a
+ * culled pixel is exactly the background.  No near plane (front_clip_plane stays unused) and no
+ * off-centre frustum.  VR_EINVAL with VR_MODE_VRC or VR_MODE_TEST, and together with VR_FLAG_CONIC or
+ * VR_FLAG_SHADE; vr_axis_columns_plan and vr_column_fused_plan report no column path. */
 /* Without VR_FLAG_ERT the march is back to front exactly like blendSampleColors. */
 
 /* ---- output flags (vr_render's out_flags, vr_render_tiles / vr_assemble_tiles) ------------- */
@@ -784,6 +815,14 @@ int vr_nifti_read(const char* path, int64_t dims[3], double* cal_max, float* vox
  * D into *depth.  Returns the number of entries (3 * 2^D). */
 int vr_octree_leaf_maps(int64_t d1, int64_t d2, int64_t d3, int32_t* maps, int64_t capacity,
                         uint32_t* depth);
+
+/* The screen of a VR_FLAG_PERSP frame from a vertical field of view, on the host (no GPU, no context):
+ * *rsh = (float)(2.0 * viewplane_distance * tan(fov_y_degrees * pi / 360)) and *rsw = (float)((double)*rsh *
+ * width / height), computed in double: vr_params.real_screen_height / real_screen_width of a frame whose
+ * rays span fov_y_degrees from top to bottom.  VR_EINVAL for a null pointer, a non-finite argument, a
+ * fov_y_degrees outside (0, 180), or a non-positive width or height. */
+int vr_persp_screen(float fov_y_degrees, int32_t width, int32_t height, float viewplane_distance, float* rsw,
+                    float* rsh);
 
 /* ---- introspection / measurement ---------------------------------------------------------- */
 int vr_get_volume_info(vr_ctx* ctx, vr_volume_info* out);

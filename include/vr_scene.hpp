@@ -150,7 +150,9 @@ public:
     ~VolumeRenderer() { vr_destroy(ctx_); }   // deallocateDeviceMemory (kernel.cu:1072-1093)
 
     // getSampleColors / getSampleColorsFromNF + blendSampleColors + the D2H copy
-    // (myApp.cu:883-915): host frame [(x*H + y)*4 + c], alpha 1
+    // (myApp.cu:883-915): host frame [(x*H + y)*4 + c], alpha 1.  The flags are vr_api.h's own (this header
+    // mirrors none): the field modes take perspective rays with p.flags |= VR_FLAG_PERSP, their screen
+    // p.real_screen_width / _height from vr_persp_screen
     std::vector<float> render(const vr_params& p, const vr_camera& cam) {
         std::vector<float> frame((size_t)p.width * p.height * 4);
         check(vr_render(ctx_, &p, &cam, frame.data(), 0), "vr_render");

@@ -4,7 +4,9 @@
 usage: tools/isa_compare.py A.s B.s [--trailing 0|1[,0|1...]]
 
 A template kernel is paired by its template arguments (the kernels' names may differ: sdvr_march_kernel<...>
-in A against dvr_march_kernel<..., true> in B), any other kernel by its name.  --trailing T: B's template
+in A against dvr_march_kernel<..., true> in B), any other kernel by its name.  A boolean argument and an
+integer one pair by value (bool SEP = true in A against int LAW = 1 in B); a kernel of B alone (LAW = 2) is
+left out.  --trailing T: B's template
 kernels carry the arguments T after A's -- only B's kernels that end in T take part, with T dropped.
 
 Per pair one line: "identical", "identical up to labels and kernel-argument offsets" (with the offsets'
@@ -18,7 +20,7 @@ import argparse
 import re
 import sys
 
-TEMPLATE = re.compile(r"^_ZN2vr\d+([a-z0-9_]+?)I((?:Lb[01]E)+)E")
+TEMPLATE = re.compile(r"^_ZN2vr\d+([a-z0-9_]+?)I((?:L[bi]\d+E)+)E")
 PLAIN = re.compile(r"^_ZN2vr\d+([a-z0-9_]+?)E")
 LBB = re.compile(r"\bL?BB\d+_")   # (.LBB<n>_<block>, and BB<n>_<block> in the loop comments)
 SLOAD = re.compile(r"^(\s*s_load_dword(?:x\d+)?\s+\S+,\s*s\[(\d+):\d+\],\s*)(0x[0-9a-f]+|\d+)(.*)$")
@@ -68,7 +70,7 @@ def key_of(name, trailing=None):
     """(display name, pairing key) of a mangled kernel name; None if --trailing leaves the kernel out."""
     m = TEMPLATE.match(name)
     if m:
-        args = tuple(int(a[2]) for a in re.findall(r"Lb[01]E", m.group(2)))
+        args = tuple(int(a) for a in re.findall(r"L[bi](\d+)E", m.group(2)))
         shown = "%s<%s>" % (m.group(1), ", ".join(map(str, args)))
         if trailing is not None:
             if args[len(args) - len(trailing):] != trailing:

@@ -1033,6 +1033,39 @@ int project_box_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam, 
     Li[1][1] = (L[0][0] * L[2][2] - L[0][2] * L[2][0]) / det;
     Li[1][2] = (L[0][2] * L[1][0] - L[0][0] * L[1][2]) / det;
     const double t[3] = {M[12], M[13], M[14]};
+    if (p->flags & VR_FLAG_PERSP) {
+        // Perspective rays: p = T V (ax t, ay t, -vpd t, 1), so a corner's camera-space point
+        // (x_cam, y_cam, z_cam) = V^-1 T^-1 p lies at t = z_cam / (-vpd) on the ray with ax = x_cam / t,
+        // ay = y_cam / t, pixel ((ax + rsw / 2) W / rsw, (ay + rsh / 2) H / rsh).  A claim only when every
+        // corner lies at or beyond sample 1 (t >= 1 / S), in front of the eye: the projection of the box is
+        // then the convex hull of the projected corners, and the rectangle and the hull edges hold as they
+        // are.  Otherwise (the eye in or beside the box) no claim: every tile is kept.
+        const double* V = B;   // inverse(lookAt): rotation + translation
+        const double R[3][3] = {{V[0], V[4], V[8]}, {V[1], V[5], V[9]}, {V[2], V[6], V[10]}};
+        const double dv = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
+                          R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
+        if (!std::isfinite(dv) || std::fabs(dv) < 1e-30) return 2;
+        double Ri[3][3];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {   // cofactors, cyclic indices
+                const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+                Ri[j][i] = (R[i1][j1] * R[i2][j2] - R[i1][j2] * R[i2][j1]) / dv;
+            }
+        const double rsw = p->real_screen_width, rsh = p->real_screen_height, vpd = p->viewplane_distance;
+        const double tmin = 1.0 / (double)p->samples_per_ray;
+        for (int k = 0; k < 8; ++k) {
+            double q[3], cc[3];
+            for (int a = 0; a < 3; ++a)
+                q[a] = ((((k >> a) & 1) ? bhi[a] : blo[a]) - Cm[12 + a]) / Cm[5 * a] - V[12 + a];
+            for (int r = 0; r < 3; ++r) cc[r] = Ri[r][0] * q[0] + Ri[r][1] * q[1] + Ri[r][2] * q[2];
+            const double tc = cc[2] / -vpd;
+            if (!(tc >= tmin)) return 2;   // (a NaN too)
+            xy[k][0] = (cc[0] / tc + rsw / 2) * p->width / rsw;
+            xy[k][1] = (cc[1] / tc + rsh / 2) * p->height / rsh;
+            if (!std::isfinite(xy[k][0]) || !std::isfinite(xy[k][1])) return 2;
+        }
+        return 1;
+    }
     for (int k = 0; k < 8; ++k) {
         double v[3];
         for (int a = 0; a < 3; ++a) v[a] = (((k >> a) & 1) ? bhi[a] : blo[a]) - t[a];
@@ -1261,10 +1294,13 @@ void check_params(const vr_params* p) {
     if (p->mode != VR_MODE_VRC && p->mode != VR_MODE_TEST && p->mode != VR_MODE_DVR && p->mode != VR_MODE_MIP &&
         p->mode != VR_MODE_ISO && p->mode != VR_MODE_SDVR && p->mode != VR_MODE_CDVR && p->mode != VR_MODE_SCDVR)
         throw Error(VR_EINVAL, "vr_params: unknown mode");
-    if (p->flags & ~(VR_FLAG_ESS | VR_FLAG_ERT | VR_FLAG_SHADE | VR_FLAG_CONIC))
+    if (p->flags & ~(VR_FLAG_ESS | VR_FLAG_ERT | VR_FLAG_SHADE | VR_FLAG_CONIC | VR_FLAG_PERSP))
         throw Error(VR_EINVAL, "vr_params: unknown flags");
     if ((p->flags & (VR_FLAG_SHADE | VR_FLAG_CONIC)) && p->mode != VR_MODE_VRC)
         throw Error(VR_EINVAL, "vr_params: VR_FLAG_SHADE / VR_FLAG_CONIC are defined for VR_MODE_VRC only");
+    // (with VR_FLAG_SHADE or VR_FLAG_CONIC no mode is left: those are VRC's, this one the field modes')
+    if ((p->flags & VR_FLAG_PERSP) && !mode_field(p))
+        throw Error(VR_EINVAL, "vr_params: VR_FLAG_PERSP is defined for the six field modes only");
 }
 
 VrcFrame make_vrc(const vr_ctx* c, const vr_params* p, const vr_camera* cam) {
@@ -1420,6 +1456,14 @@ TestFrame make_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam) {
         for (int i : {0, 5, 10, 12, 13, 14}) sep = sep && std::isfinite(f.mc[i]) && std::isfinite(f.tv[i]);
         for (int i = 0; i < 16; ++i) sep = sep && std::isfinite(f.iv[i]);
         f.sep = sep ? 1 : 0;
+        // VR_FLAG_PERSP (the field modes): the perspective law, whatever the matrices hold (it reads SEP's
+        // entries; a non-finite one gives NaN positions, samples outside the volume), t(s) = fs * rS
+        const bool persp = (p->flags & VR_FLAG_PERSP) != 0;
+        if (persp) {
+            sep = true;
+            f.sep = 2;   // (vr_march.h kLawPersp)
+            f.rS = 1.0f / (float)f.S;
+        }
         // the general march's per-frame table of the ray-independent half of the position: 16 B per
         // sample of [-4, S + 4) in LDS, bounded (unbounded it failed the launch from
         // S ~ 9k); longer rays compute it per sample with the same expressions
@@ -1452,7 +1496,8 @@ TestFrame make_test(const vr_ctx* c, const vr_params* p, const vr_camera* cam) {
         // voxel i0 < d_a sits below the 2-bit delta at bit 29; 2^29 would be exact too, 2^28 keeps
         // one bit of margin).  Along x and y the two z corners of a line pair are read as one dword.
         f.axt = -1;
-        const bool common = f.sep && f.S <= 4096 && !f.idx64 && f.cls0 == 0 && f.zero_transparent && c->test_axz;
+        // (perspective rays are not parallel: no axis view)
+        const bool common = f.sep == 1 && f.S <= 4096 && !f.idx64 && f.cls0 == 0 && f.zero_transparent && c->test_axz;
         for (int a = 2; a >= 0 && common && f.axt < 0; --a) {
             const int b = a == 0 ? 1 : 0, cc = a == 2 ? 1 : 2;
             auto fixed = [&](int r) { return f.iv[8 + r] == 0.0f && (!negzero(f.iv[12 + r]) || f.tv[12 + r] != 0.0f); };
@@ -3343,6 +3388,18 @@ int vr_camera_derive(const float pos[3], const float up[3], float rsw, float rsh
 int vr_camera_derive_conic(const float pos[3], const float up[3], float rsw, float rsh, float vpd, vr_camera* out) {
     if (!pos || !up || !out) return VR_EINVAL;
     put(derive_camera_conic({pos[0], pos[1], pos[2]}, {up[0], up[1], up[2]}, rsw, rsh, vpd), out);
+    return VR_OK;
+}
+
+int vr_persp_screen(float fov_y_degrees, int32_t width, int32_t height, float viewplane_distance, float* rsw,
+                    float* rsh) {
+    if (!rsw || !rsh || width <= 0 || height <= 0) return VR_EINVAL;
+    if (!std::isfinite(fov_y_degrees) || !std::isfinite(viewplane_distance)) return VR_EINVAL;
+    if (!(fov_y_degrees > 0.0f && fov_y_degrees < 180.0f)) return VR_EINVAL;
+    const double pi = 3.14159265358979323846;
+    const float h = (float)(2.0 * (double)viewplane_distance * std::tan((double)fov_y_degrees * pi / 360.0));
+    *rsh = h;
+    *rsw = (float)((double)h * (double)width / (double)height);
     return VR_OK;
 }
 

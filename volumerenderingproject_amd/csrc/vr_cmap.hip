@@ -62,7 +62,7 @@ namespace vr {
 // ------------------------------------------------------------------------------------------------
 constexpr int kCmapK = 4;
 
-template <bool F2B, bool ESS, bool U8, bool SMALL, bool SEP, bool SHADE, bool CROP>
+template <bool F2B, bool ESS, bool U8, bool SMALL, int LAW, bool SHADE, bool CROP>
 __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame g, ScdvrFrame h,
                                                          const WorkTile* __restrict__ work,
                                                          const void* __restrict__ vol,
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
     constexpr int K = kCmapK;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
     // LDS: G's points (SHADE) | the points' colours | their (x, inv) | the cell bits (ESS) | the B
-    // table (SEP)
+    // table (SEP, PERSP)
     float4* s_G = reinterpret_cast<float4*>(smem_all);
     unsigned char* smem = smem_all + (SHADE ? kGopaLds : 0);
     float4* s_col = reinterpret_cast<float4*>(smem);
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
     }
     if (occ_st)
         for (int i = threadIdx.x + 4 * kWgThreads; i < f.occ_words; i += kWgThreads) s_occ[i] = gocc[i];
-    if (SEP && f.sep_tab) test_stage_B(f, s_B, K);
+    if (LAW != kLawGeneral && f.sep_tab) test_stage_B<LAW>(f, s_B, K);
     __syncthreads();
     const __amdgpu_buffer_rsrc_t ors = uniform_rsrc(gocc, ESS ? f.occ_words * 4 : 0);
     auto occ_word = [&](int wi) -> uint32_t {
@@ -135,8 +135,8 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
 
     // TEST's position chain, clip and linear model (vr_march.h)
     TestRay ray;
-    test_ray_init<SEP>(f, x, y, ray);
-    auto position = [&](int s, float p[3]) { test_position<SEP>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
+    test_ray_init<LAW>(f, x, y, ray);
+    auto position = [&](int s, float p[3]) { test_position<LAW>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
     int s_begin, s_end;
     float pa[3], dp[3], idp[3];
     float L[3] = {0.0f, 0.0f, 0.0f};
@@ -334,7 +334,7 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
                     // table -- the same floats -- and the 16 SGPRs go to the rest)
                     int jg = 0;   // the points m_i <= mag (a NaN: none)
 #pragma unroll
-                    for (int i = 0; i < kMaxGopa; ++i) jg += (int)(mag >= ((CROP && !SEP) ? s_G[i].x : h.m[i]));
+                    for (int i = 0; i < kMaxGopa; ++i) jg += (int)(mag >= ((CROP && LAW == kLawGeneral) ? s_G[i].x : h.m[i]));
                     const float4 ge = s_G[max(jg - 1, 0)];
                     const float ug = fminf((mag - ge.x) * ge.y, 1.0f);
                     const float ug1 = 1.0f - ug;
@@ -428,16 +428,16 @@ hipError_t launch_cmap_march(const TestFrame& f, const CmapFrame& g, const Scdvr
                              int n_blocks, const void* vol, bool u8, const float2* xi, const float4* col,
                              const uint32_t* occ, float4* out, hipStream_t st, const CropBox* crop) {
     const bool f2b = (f.flags & 2) != 0, ess = (f.flags & 1) != 0 && f.zero_transparent && occ != nullptr;
-    const bool small = g.n <= kCmapSmall, sep = f.sep != 0;
+    const bool small = g.n <= kCmapSmall;
     const size_t lds = cmap_lds_bytes(f, g, ess, shade != nullptr);
     const ScdvrFrame h = shade ? *shade : ScdvrFrame{};
     const CropBox cb = crop ? *crop : CropBox{};
-#define VR_C7(F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_, CROP_)                                                 \
-    hipLaunchKernelGGL((cmap_march_kernel<F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_, CROP_>), dim3(n_blocks),    \
+#define VR_C7(F2B_, ESS_, U8_, SMALL_, LAW_, SHADE_, CROP_)                                                 \
+    hipLaunchKernelGGL((cmap_march_kernel<F2B_, ESS_, U8_, SMALL_, LAW_, SHADE_, CROP_>), dim3(n_blocks),    \
                        dim3(kWgThreads), lds, st, f, g, h, work, vol, xi, col, occ, out, cb)
-#define VR_C6(F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_) do { if (crop) VR_C7(F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_, true); else VR_C7(F2B_, ESS_, U8_, SMALL_, SEP_, SHADE_, false); } while (0)
-#define VR_C5(F2B_, ESS_, U8_, SMALL_, SEP_) do { if (shade) VR_C6(F2B_, ESS_, U8_, SMALL_, SEP_, true); else VR_C6(F2B_, ESS_, U8_, SMALL_, SEP_, false); } while (0)
-#define VR_C4(F2B_, ESS_, U8_, SMALL_) do { if (sep) VR_C5(F2B_, ESS_, U8_, SMALL_, true); else VR_C5(F2B_, ESS_, U8_, SMALL_, false); } while (0)
+#define VR_C6(F2B_, ESS_, U8_, SMALL_, LAW_, SHADE_) do { if (crop) VR_C7(F2B_, ESS_, U8_, SMALL_, LAW_, SHADE_, true); else VR_C7(F2B_, ESS_, U8_, SMALL_, LAW_, SHADE_, false); } while (0)
+#define VR_C5(F2B_, ESS_, U8_, SMALL_, LAW_) do { if (shade) VR_C6(F2B_, ESS_, U8_, SMALL_, LAW_, true); else VR_C6(F2B_, ESS_, U8_, SMALL_, LAW_, false); } while (0)
+#define VR_C4(F2B_, ESS_, U8_, SMALL_) do { if (f.sep == kLawPersp) VR_C5(F2B_, ESS_, U8_, SMALL_, kLawPersp); else if (f.sep) VR_C5(F2B_, ESS_, U8_, SMALL_, kLawSep); else VR_C5(F2B_, ESS_, U8_, SMALL_, kLawGeneral); } while (0)
 #define VR_C3(F2B_, ESS_, U8_) do { if (small) VR_C4(F2B_, ESS_, U8_, true); else VR_C4(F2B_, ESS_, U8_, false); } while (0)
 #define VR_C2(F2B_, ESS_) do { if (u8) VR_C3(F2B_, ESS_, true); else VR_C3(F2B_, ESS_, false); } while (0)
     if (f2b) { if (ess) VR_C2(true, true); else VR_C2(true, false); }

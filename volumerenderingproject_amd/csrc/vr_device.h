@@ -158,6 +158,8 @@ struct TestFrame {
     float mc[16], iv[16], tv[16];   // modelCam, inverse(lookAt), toVolume; column-major
     float bg[4];
     float ert_eps;
+    float rS;                       // VR_FLAG_PERSP: 1.0f / (float)S, t(s) = fs * rS (in the padding ahead of d1:
+                                    // no other field's offset moves); 0 otherwise
     int64_t d1, d2, d3, total;
     float fd1, fd2, fd3;
     int32_t zero_transparent;
@@ -167,7 +169,9 @@ struct TestFrame {
     int32_t idx64;                  // 64-bit corner indices (total + d2*d3 + d3 >= 2^31)
     int32_t tcb, tnc[3];            // ESS macro cells: 2^tcb voxels per axis, cells per axis
     int32_t occ_words, occ_lds;
-    int32_t sep;                    // mc and tv are axis-separable (scale + translate): see test_march_kernel
+    int32_t sep;                    // mc and tv are axis-separable (scale + translate): see test_march_kernel;
+                                    // the field marches' position law (vr_march.h kLawGeneral / kLawSep / kLawPersp):
+                                    // 2 under VR_FLAG_PERSP, whatever the matrices hold
     int32_t sep_tab;                // sep + the per-frame B table fits its LDS budget (S + 8 <= kMaxTestTab)
     int32_t axt;                    // -1, or the volume axis a along which the rays march with the other two
                                     // coordinates of p fixed (test_axis_kernel; make_test's conditions)

@@ -62,7 +62,7 @@ namespace vr {
 // ------------------------------------------------------------------------------------------------
 constexpr int kDvrK = 4;
 
-template <bool F2B, bool ESS, bool U8, bool SEG8, bool SEP, bool SHADE, bool CROP>
+template <bool F2B, bool ESS, bool U8, bool SEG8, int LAW, bool SHADE, bool CROP>
 __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g, SdvrFrame h,
                                                         const WorkTile* __restrict__ work,
                                                         const void* __restrict__ vol,
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g,
                                                         float4* __restrict__ out, CropBox cb) {
     constexpr int K = kDvrK;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // LDS: the segments' colours | their starts (search only) | the cell bits (ESS) | the B table (SEP)
+    // LDS: the segments' colours | their starts (search only) | the cell bits (ESS) | the B table (SEP, PERSP)
     float4* s_seg = reinterpret_cast<float4*>(smem);
     float* s_start = reinterpret_cast<float*>(smem + (size_t)g.nseg * sizeof(float4));
     const bool occ_st = ESS && f.occ_lds;
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g,
     }
     if (occ_st)
         for (int i = threadIdx.x + 4 * kWgThreads; i < f.occ_words; i += kWgThreads) s_occ[i] = gocc[i];
-    if (SEP && f.sep_tab) test_stage_B(f, s_B, K);
+    if (LAW != kLawGeneral && f.sep_tab) test_stage_B<LAW>(f, s_B, K);
     __syncthreads();
     const __amdgpu_buffer_rsrc_t ors = uniform_rsrc(gocc, ESS ? f.occ_words * 4 : 0);
     auto occ_word = [&](int wi) -> uint32_t {
@@ -135,8 +135,8 @@ __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g,
 
     // TEST's position chain, clip and linear model (vr_march.h)
     TestRay ray;
-    test_ray_init<SEP>(f, x, y, ray);
-    auto position = [&](int s, float p[3]) { test_position<SEP>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
+    test_ray_init<LAW>(f, x, y, ray);
+    auto position = [&](int s, float p[3]) { test_position<LAW>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
     int s_begin, s_end;
     float pa[3], dp[3], idp[3];
     float L[3] = {0.0f, 0.0f, 0.0f};
@@ -446,16 +446,16 @@ hipError_t launch_dvr_march(const TestFrame& f, const DvrFrame& g, const SdvrFra
                             int n_blocks, const void* vol, bool u8, const float* start, const float4* seg,
                             const uint32_t* occ, float4* out, hipStream_t st, const CropBox* crop) {
     const bool f2b = (f.flags & 2) != 0, ess = (f.flags & 1) != 0 && f.zero_transparent && occ != nullptr;
-    const bool seg8 = g.nseg <= 1 + kDvrSeg8, sep = f.sep != 0;
+    const bool seg8 = g.nseg <= 1 + kDvrSeg8;
     const size_t lds = dvr_lds_bytes(f, g, ess);
     const SdvrFrame h = shade ? *shade : SdvrFrame{};
     const CropBox cb = crop ? *crop : CropBox{};
-#define VR_D7(F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_, CROP_)                                                  \
-    hipLaunchKernelGGL((dvr_march_kernel<F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_, CROP_>), dim3(n_blocks),      \
+#define VR_D7(F2B_, ESS_, U8_, SEG8_, LAW_, SHADE_, CROP_)                                                  \
+    hipLaunchKernelGGL((dvr_march_kernel<F2B_, ESS_, U8_, SEG8_, LAW_, SHADE_, CROP_>), dim3(n_blocks),      \
                        dim3(kWgThreads), lds, st, f, g, h, work, vol, start, seg, occ, out, cb)
-#define VR_D6(F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_) do { if (crop) VR_D7(F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_, true); else VR_D7(F2B_, ESS_, U8_, SEG8_, SEP_, SHADE_, false); } while (0)
-#define VR_D5(F2B_, ESS_, U8_, SEG8_, SEP_) do { if (shade) VR_D6(F2B_, ESS_, U8_, SEG8_, SEP_, true); else VR_D6(F2B_, ESS_, U8_, SEG8_, SEP_, false); } while (0)
-#define VR_D4(F2B_, ESS_, U8_, SEG8_) do { if (sep) VR_D5(F2B_, ESS_, U8_, SEG8_, true); else VR_D5(F2B_, ESS_, U8_, SEG8_, false); } while (0)
+#define VR_D6(F2B_, ESS_, U8_, SEG8_, LAW_, SHADE_) do { if (crop) VR_D7(F2B_, ESS_, U8_, SEG8_, LAW_, SHADE_, true); else VR_D7(F2B_, ESS_, U8_, SEG8_, LAW_, SHADE_, false); } while (0)
+#define VR_D5(F2B_, ESS_, U8_, SEG8_, LAW_) do { if (shade) VR_D6(F2B_, ESS_, U8_, SEG8_, LAW_, true); else VR_D6(F2B_, ESS_, U8_, SEG8_, LAW_, false); } while (0)
+#define VR_D4(F2B_, ESS_, U8_, SEG8_) do { if (f.sep == kLawPersp) VR_D5(F2B_, ESS_, U8_, SEG8_, kLawPersp); else if (f.sep) VR_D5(F2B_, ESS_, U8_, SEG8_, kLawSep); else VR_D5(F2B_, ESS_, U8_, SEG8_, kLawGeneral); } while (0)
 #define VR_D3(F2B_, ESS_, U8_) do { if (seg8) VR_D4(F2B_, ESS_, U8_, true); else VR_D4(F2B_, ESS_, U8_, false); } while (0)
 #define VR_D2(F2B_, ESS_) do { if (u8) VR_D3(F2B_, ESS_, true); else VR_D3(F2B_, ESS_, false); } while (0)
     if (f2b) { if (ess) VR_D2(true, true); else VR_D2(true, false); }

@@ -45,17 +45,10 @@ constexpr int kIsoK = 4;
 
 // p = T * (V * (Mcam * (x, y, fs, 1))) at a float sample coordinate: test_position's expressions
 // without the table
-template <bool SEP>
+template <int LAW>
 __device__ __forceinline__ void iso_position(const TestFrame& f, const TestRay& ray, float fs, float p[3]) {
-    if (SEP) {
-        const float4 Bs = test_B_entry(f, fs);
-        float q2[3];
-        q2[0] = ray.A[0] + Bs.x;
-        q2[1] = ray.A[1] + Bs.y;
-        q2[2] = ray.A[2] + Bs.z;
-        p[0] = f.tv[0] * q2[0] + f.tv[12];
-        p[1] = f.tv[5] * q2[1] + f.tv[13];
-        p[2] = f.tv[10] * q2[2] + f.tv[14];
+    if (LAW != kLawGeneral) {   // (PERSP: t(fs) in the entry's fourth float)
+        test_position_of<LAW>(f, ray, test_B_entry<LAW>(f, fs), p);
         return;
     }
     float q1[3], q2[3];
@@ -79,18 +72,18 @@ __device__ __forceinline__ bool iso_inside(const TestFrame& f, const CropBox& cb
 
 // (ESS, U8, SEP -- the flagship path -- allocates 80 VGPRs left to itself, 6 waves per SIMD where MIP's
 // twin has 7; held to 7 waves it fits 72 without scratch.  The other instantiations are left alone.)
-template <bool ESS, bool U8, bool SEP, bool CROP>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ESS && U8 && SEP ? 7 : 1)))
+template <bool ESS, bool U8, int LAW, bool CROP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ESS && U8 && LAW == kLawSep ? 7 : 1)))
 void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work, const void* __restrict__ vol,
                       const float* __restrict__ gbound, float4* __restrict__ out, CropBox cb) {
     constexpr int K = kIsoK;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float4* s_B = reinterpret_cast<float4*>(smem);   // LDS: the B table (SEP) only
+    float4* s_B = reinterpret_cast<float4*>(smem);   // LDS: the B table (SEP, PERSP) only
     const int b = (int)blockIdx.x;
     const WorkTile wt = work[b < f.n_work ? b : 0];
     if (b >= f.n_work) return;
     if (test_background(f, work, wt, out)) return;
-    if (SEP && f.sep_tab) test_stage_B(f, s_B, K);
+    if (LAW != kLawGeneral && f.sep_tab) test_stage_B<LAW>(f, s_B, K);
     __syncthreads();
     int x, y;
     ray_of_thread(wt, x, y);
@@ -98,8 +91,8 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
 
     // TEST's position chain, clip and linear model (vr_march.h)
     TestRay ray;
-    test_ray_init<SEP>(f, x, y, ray);
-    auto position = [&](int s, float p[3]) { test_position<SEP>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
+    test_ray_init<LAW>(f, x, y, ray);
+    auto position = [&](int s, float p[3]) { test_position<LAW>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
     int s_begin, s_end;
     float pa[3], dp[3], idp[3];
     {
@@ -230,7 +223,7 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
         bool refinable = false;
         if (sh > 0) {
             float pp[3];
-            iso_position<SEP>(f, ray, (float)(sh - 1), pp);
+            iso_position<LAW>(f, ray, (float)(sh - 1), pp);
             refinable = iso_inside<CROP>(f, cb, pp[0], pp[1], pp[2]);
             lo = refinable ? (float)(sh - 1) : hi;
         }
@@ -238,7 +231,7 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
         for (int it = 0; it < kIsoRefine; ++it) {
             const float mid = (lo + hi) * 0.5f;
             float pm[3];
-            iso_position<SEP>(f, ray, mid, pm);
+            iso_position<LAW>(f, ray, mid, pm);
             const bool ok = iso_inside<CROP>(f, cb, pm[0], pm[1], pm[2]);
             const float v = field_value_at<U8>(ok, pm[0], pm[1], pm[2], vrs, d3, d23, xl, yl, zl);
             const bool take = ok && v >= iso;
@@ -246,7 +239,7 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
             lo = (refinable && !take) ? mid : lo;
         }
         float ps[3];
-        iso_position<SEP>(f, ray, hi, ps);
+        iso_position<LAW>(f, ray, hi, ps);
 
         // gradient of the trilinear field at p*: taps t = 2 a (q+) and 2 a + 1 (q-) of axis a, both in
         // the volume (selects, no indexed arrays: the loop is rolled)
@@ -279,8 +272,8 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
 
         // headlight along the ray, in voxel space
         float pe[3], p0[3], L[3] = {0.0f, 0.0f, 0.0f};
-        iso_position<SEP>(f, ray, (float)(f.S > 1 ? f.S - 1 : 0), pe);
-        iso_position<SEP>(f, ray, 0.0f, p0);
+        iso_position<LAW>(f, ray, (float)(f.S > 1 ? f.S - 1 : 0), pe);
+        iso_position<LAW>(f, ray, 0.0f, p0);
         const float ex = pe[0] - p0[0], ey = pe[1] - p0[1], ez = pe[2] - p0[2];
         const float n2 = (ex * ex + ey * ey) + ez * ez;
         if (n2 > 0.0f) {
@@ -301,14 +294,14 @@ void iso_march_kernel(TestFrame f, IsoFrame g, const WorkTile* __restrict__ work
 
 hipError_t launch_iso_march(const TestFrame& f, const IsoFrame& g, const WorkTile* work, int n_blocks, const void* vol,
                             bool u8, const float* bound, float4* out, hipStream_t st, const CropBox* crop) {
-    const bool ess = (f.flags & 1) != 0 && bound != nullptr, sep = f.sep != 0;
+    const bool ess = (f.flags & 1) != 0 && bound != nullptr;
     const CropBox cb = crop ? *crop : CropBox{};   // (null: the box is off, the CROP = false instantiations)
     const size_t lds = (f.sep && f.sep_tab) ? (size_t)(f.S + 2 * kIsoK) * sizeof(float4) : 0;
-#define VR_I4(ESS_, U8_, SEP_, CROP_)                                                                  \
-    hipLaunchKernelGGL((iso_march_kernel<ESS_, U8_, SEP_, CROP_>), dim3(n_blocks), dim3(kWgThreads), lds, st, f, \
+#define VR_I4(ESS_, U8_, LAW_, CROP_)                                                                  \
+    hipLaunchKernelGGL((iso_march_kernel<ESS_, U8_, LAW_, CROP_>), dim3(n_blocks), dim3(kWgThreads), lds, st, f, \
                        g, work, vol, bound, out, cb)
-#define VR_I3(ESS_, U8_, SEP_) do { if (crop) VR_I4(ESS_, U8_, SEP_, true); else VR_I4(ESS_, U8_, SEP_, false); } while (0)
-#define VR_I2(ESS_, U8_) do { if (sep) VR_I3(ESS_, U8_, true); else VR_I3(ESS_, U8_, false); } while (0)
+#define VR_I3(ESS_, U8_, LAW_) do { if (crop) VR_I4(ESS_, U8_, LAW_, true); else VR_I4(ESS_, U8_, LAW_, false); } while (0)
+#define VR_I2(ESS_, U8_) do { if (f.sep == kLawPersp) VR_I3(ESS_, U8_, kLawPersp); else if (f.sep) VR_I3(ESS_, U8_, kLawSep); else VR_I3(ESS_, U8_, kLawGeneral); } while (0)
 #define VR_I1(ESS_) do { if (u8) VR_I2(ESS_, true); else VR_I2(ESS_, false); } while (0)
     if (ess) VR_I1(true); else VR_I1(false);
 #undef VR_I1

@@ -142,8 +142,15 @@ __device__ __forceinline__ void mulv3(const float* m, float x, float y, float z,
 struct TestRay {
     float add0[3], A[3];
 };
-template <bool SEP>
+// The position law of the field marches, a template argument of theirs (the host's TestFrame.sep): the
+// general chain, its separable form (SEP, below), or -- VR_FLAG_PERSP -- the separable form with the per-ray
+// half A_r scaled by t(s) = fs * rS: q_r = A_r * t + B_r, rays from the one eye p(x, y, 0) through the
+// orthographic screen at fs = S.  PERSP reads the entries of mc and tv that SEP reads and has no general
+// variant.  Three values of one argument, not a second boolean: the instantiations grow by half, not double.
+constexpr int kLawGeneral = 0, kLawSep = 1, kLawPersp = 2;
+template <int LAW>
 __device__ __forceinline__ void test_ray_init(const TestFrame& f, int x, int y, TestRay& ray) {
+    constexpr bool SEP = LAW != kLawGeneral;
     const float fx = (float)x, fy = (float)y;
     // first product, split: Add0 = m0*x + m1*y per ray; Add1 = m2*s + m3 per sample
 #pragma unroll
@@ -163,33 +170,48 @@ __device__ __forceinline__ void test_ray_init(const TestFrame& f, int x, int y, 
 
 // SEP: the per-sample half of the second product, B_r(s) = iv_{8+r} q1z(s) + iv_{12+r} with
 // q1z(s) = mc10 s + mc14, is the same for every ray: entry j of the per-frame LDS table (sample
-// s = j - K, for s in [-K, S + K))
+// s = j - K, for s in [-K, S + K)); its fourth float is 0, or -- PERSP -- t(s) = fs * rS
+template <int LAW>
 __device__ __forceinline__ float4 test_B_entry(const TestFrame& f, float fs) {
     const float q1z = f.mc[10] * fs + f.mc[14];
     return make_float4(f.iv[8] * q1z + f.iv[12] * 1.0f, f.iv[9] * q1z + f.iv[13] * 1.0f,
-                       f.iv[10] * q1z + f.iv[14] * 1.0f, 0.0f);
+                       f.iv[10] * q1z + f.iv[14] * 1.0f, LAW == kLawPersp ? fs * f.rS : 0.0f);
 }
+template <int LAW>
 __device__ __forceinline__ void test_stage_B(const TestFrame& f, float4* s_B, int K) {
-    for (int j = threadIdx.x; j < f.S + 2 * K; j += kWgThreads) s_B[j] = test_B_entry(f, (float)(j - K));
+    for (int j = threadIdx.x; j < f.S + 2 * K; j += kWgThreads) s_B[j] = test_B_entry<LAW>(f, (float)(j - K));
+}
+
+// SEP and PERSP: p_r = tv_rr q2_r + tv_3r from a B entry: q2_r = A_r + B_r, or -- PERSP -- A_r * t + B_r,
+// every product and sum rounded on its own
+template <int LAW>
+__device__ __forceinline__ void test_position_of(const TestFrame& f, const TestRay& ray, const float4 Bs, float p[3]) {
+    float q2[3];
+    if (LAW == kLawPersp) {
+        q2[0] = ray.A[0] * Bs.w + Bs.x;
+        q2[1] = ray.A[1] * Bs.w + Bs.y;
+        q2[2] = ray.A[2] * Bs.w + Bs.z;
+    } else {
+        q2[0] = ray.A[0] + Bs.x;
+        q2[1] = ray.A[1] + Bs.y;
+        q2[2] = ray.A[2] + Bs.z;
+    }
+    p[0] = f.tv[0] * q2[0] + f.tv[12];
+    p[1] = f.tv[5] * q2[1] + f.tv[13];
+    p[2] = f.tv[10] * q2[2] + f.tv[14];
 }
 
 // p = T * (V * (Mcam * (x, y, s, 1))) for sample s in [-K, S + K); tab: B_r(s) from the LDS table
 // (without it -- long rays: it would not fit LDS -- the same expressions per sample)
-template <bool SEP>
+template <int LAW>
 __device__ __forceinline__ void test_position(const TestFrame& f, const TestRay& ray, const float4* s_B, bool tab,
                                               int K, int s, float p[3]) {
     const float fs = (float)s;
-    if (SEP) {
+    if (LAW != kLawGeneral) {
         float4 Bs;
         if (tab) Bs = s_B[s + K];
-        else Bs = test_B_entry(f, fs);
-        float q2[3];
-        q2[0] = ray.A[0] + Bs.x;
-        q2[1] = ray.A[1] + Bs.y;
-        q2[2] = ray.A[2] + Bs.z;
-        p[0] = f.tv[0] * q2[0] + f.tv[12];
-        p[1] = f.tv[5] * q2[1] + f.tv[13];
-        p[2] = f.tv[10] * q2[2] + f.tv[14];
+        else Bs = test_B_entry<LAW>(f, fs);
+        test_position_of<LAW>(f, ray, Bs, p);
         return;
     }
     float q1[3], q2[3];
@@ -205,7 +227,8 @@ __device__ __forceinline__ void test_position(const TestFrame& f, const TestRay&
 // few ulps of |p| (~1e-5 voxel), the float quotients by ~1e-7 of s (< 1e-3 samples at S = 9k) -- far
 // inside the 0.01-voxel and floor - 1 / ceil + 2 margins.  A zero step tests the point; a denormal
 // one gives an infinite reciprocal, whose products keep the test conservative (a NaN from 0 * inf
-// is ignored by fminf / fmaxf: no constraint).
+// is ignored by fminf / fmaxf: no constraint).  PERSP: p(s) is affine in s in real arithmetic too (t and
+// B are), and its two more roundings (t, A_r * t) are again ulps of |p|: the same margins hold.
 __device__ __forceinline__ void test_clip(const TestFrame& f, const float pa[3], const float pb[3], float dp[3],
                                           float idp[3], int& s_begin, int& s_end) {
     s_begin = 0;

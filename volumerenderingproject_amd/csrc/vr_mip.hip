@@ -49,19 +49,19 @@ namespace vr {
 // ------------------------------------------------------------------------------------------------
 constexpr int kMipK = 4;
 
-template <bool ESS, bool U8, bool SEP, bool CROP>
+template <bool ESS, bool U8, int LAW, bool CROP>
 __global__ __launch_bounds__(256) void mip_march_kernel(TestFrame f, MipFrame g, const WorkTile* __restrict__ work,
                                                         const void* __restrict__ vol,
                                                         const float* __restrict__ gbound,
                                                         float4* __restrict__ out, CropBox cb) {
     constexpr int K = kMipK;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float4* s_B = reinterpret_cast<float4*>(smem);   // LDS: the B table (SEP) only
+    float4* s_B = reinterpret_cast<float4*>(smem);   // LDS: the B table (SEP, PERSP) only
     const int b = (int)blockIdx.x;
     const WorkTile wt = work[b < f.n_work ? b : 0];
     if (b >= f.n_work) return;
     if (test_background(f, work, wt, out)) return;
-    if (SEP && f.sep_tab) test_stage_B(f, s_B, K);
+    if (LAW != kLawGeneral && f.sep_tab) test_stage_B<LAW>(f, s_B, K);
     __syncthreads();
     int x, y;
     ray_of_thread(wt, x, y);
@@ -69,8 +69,8 @@ __global__ __launch_bounds__(256) void mip_march_kernel(TestFrame f, MipFrame g,
 
     // TEST's position chain, clip and linear model (vr_march.h)
     TestRay ray;
-    test_ray_init<SEP>(f, x, y, ray);
-    auto position = [&](int s, float p[3]) { test_position<SEP>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
+    test_ray_init<LAW>(f, x, y, ray);
+    auto position = [&](int s, float p[3]) { test_position<LAW>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
     int s_begin, s_end;
     float pa[3], dp[3], idp[3];
     {
@@ -237,14 +237,14 @@ __global__ __launch_bounds__(256) void mip_bounds_kernel(const float2* __restric
 
 hipError_t launch_mip_march(const TestFrame& f, const MipFrame& g, const WorkTile* work, int n_blocks, const void* vol,
                             bool u8, const float* bound, float4* out, hipStream_t st, const CropBox* crop) {
-    const bool ess = (f.flags & 1) != 0 && bound != nullptr, sep = f.sep != 0;
+    const bool ess = (f.flags & 1) != 0 && bound != nullptr;
     const CropBox cb = crop ? *crop : CropBox{};   // (null: the box is off, the CROP = false instantiations)
     const size_t lds = (f.sep && f.sep_tab) ? (size_t)(f.S + 2 * kMipK) * sizeof(float4) : 0;
-#define VR_M4(ESS_, U8_, SEP_, CROP_)                                                                  \
-    hipLaunchKernelGGL((mip_march_kernel<ESS_, U8_, SEP_, CROP_>), dim3(n_blocks), dim3(kWgThreads), lds, st, f, \
+#define VR_M4(ESS_, U8_, LAW_, CROP_)                                                                  \
+    hipLaunchKernelGGL((mip_march_kernel<ESS_, U8_, LAW_, CROP_>), dim3(n_blocks), dim3(kWgThreads), lds, st, f, \
                        g, work, vol, bound, out, cb)
-#define VR_M3(ESS_, U8_, SEP_) do { if (crop) VR_M4(ESS_, U8_, SEP_, true); else VR_M4(ESS_, U8_, SEP_, false); } while (0)
-#define VR_M2(ESS_, U8_) do { if (sep) VR_M3(ESS_, U8_, true); else VR_M3(ESS_, U8_, false); } while (0)
+#define VR_M3(ESS_, U8_, LAW_) do { if (crop) VR_M4(ESS_, U8_, LAW_, true); else VR_M4(ESS_, U8_, LAW_, false); } while (0)
+#define VR_M2(ESS_, U8_) do { if (f.sep == kLawPersp) VR_M3(ESS_, U8_, kLawPersp); else if (f.sep) VR_M3(ESS_, U8_, kLawSep); else VR_M3(ESS_, U8_, kLawGeneral); } while (0)
 #define VR_M1(ESS_) do { if (u8) VR_M2(ESS_, true); else VR_M2(ESS_, false); } while (0)
     if (ess) VR_M1(true); else VR_M1(false);
 #undef VR_M1

@@ -34,6 +34,7 @@ VR_FLAG_ESS = 1
 VR_FLAG_ERT = 2
 VR_FLAG_SHADE = 8
 VR_FLAG_CONIC = 16
+VR_FLAG_PERSP = 32    # perspective rays for the six field modes (include/vr_api.h; persp_screen)
 VR_OUT_DEVICE = 1
 VR_OUT_ASYNC = 2
 VR_OUT_RGB = 4      # tile buffers of 3 floats per pixel (alpha is 1 by construction)
@@ -53,7 +54,7 @@ EXPORTED = [
     "vr_axis_columns_plan", "vr_column_fused_plan", "vr_tf_segments", "vr_set_isosurface", "vr_get_isosurface",
     "vr_set_colormap", "vr_get_colormap", "vr_colormap_eval",
     "vr_set_gradient_opacity", "vr_get_gradient_opacity", "vr_gradient_opacity_eval",
-    "vr_set_crop_box", "vr_get_crop_box",
+    "vr_set_crop_box", "vr_get_crop_box", "vr_persp_screen",
 ]
 VR_COMM_ID_BYTES = 128
 VR_TRANSPORT_NONE, VR_TRANSPORT_RCCL, VR_TRANSPORT_PEER_COPY = 0, 1, 2
@@ -233,6 +234,7 @@ def lib():
         "vr_synthetic_volume": ([vp, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int32, vp], C.c_int),
         "vr_camera_derive_conic": ([P(C.c_float), P(C.c_float), C.c_float, C.c_float, C.c_float, P(Camera)], C.c_int),
         "vr_point_cloud": ([vp, vp, C.c_int32], C.c_int),
+        "vr_persp_screen": ([C.c_float, C.c_int32, C.c_int32, C.c_float, P(C.c_float), P(C.c_float)], C.c_int),
         "vr_visible_tiles": ([vp, P(RenderParams), P(Camera), C.c_int32, C.c_int32, P(C.c_int32), C.c_int32,
                               P(C.c_int32)], C.c_int),
         "vr_render_tile_list": ([vp, P(RenderParams), P(Camera), C.c_int32, C.c_int32, P(C.c_int32), C.c_int32,
@@ -328,11 +330,23 @@ def gradient_opacity_eval(points, mag) -> np.ndarray:
 def default_params(width, height, samples_per_ray, mode=VR_MODE_VRC, flags=0, ert_epsilon=1e-5) -> RenderParams:
     """vr_params_default with the mode (VR_MODE_VRC, _TEST, _DVR, _MIP, _ISO, _SDVR, _CDVR or _SCDVR), flags and ERT
     threshold set.  VR_MODE_ISO, VR_MODE_SDVR and VR_MODE_SCDVR always shade: they read shade_ambient /
-    _diffuse / _specular / _shininess without VR_FLAG_SHADE, which only VR_MODE_VRC accepts."""
+    _diffuse / _specular / _shininess without VR_FLAG_SHADE, which only VR_MODE_VRC accepts.  VR_FLAG_PERSP
+    (the six field modes only, not with VR_FLAG_CONIC or VR_FLAG_SHADE) takes perspective rays from the eye
+    p(x, y, 0) through the screen real_screen_width x real_screen_height at sample S: set those two from
+    persp_screen(fov_y_degrees, width, height, viewplane_distance)."""
     p = RenderParams()
     _check(lib().vr_params_default(width, height, samples_per_ray, C.byref(p)), "vr_params_default")
     p.mode, p.flags, p.ert_epsilon = mode, flags, ert_epsilon
     return p
+
+
+def persp_screen(fov_y_degrees, width, height, viewplane_distance):
+    """vr_persp_screen: (real_screen_width, real_screen_height) of a VR_FLAG_PERSP frame whose rays span
+    fov_y_degrees from top to bottom, on the host (no GPU, no context)."""
+    rsw, rsh = C.c_float(), C.c_float()
+    _check(lib().vr_persp_screen(fov_y_degrees, width, height, viewplane_distance, C.byref(rsw), C.byref(rsh)),
+           "vr_persp_screen")
+    return rsw.value, rsh.value
 
 
 def default_camera(width, height) -> Camera:
