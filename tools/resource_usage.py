@@ -3,11 +3,16 @@
 the instantiations with one template argument at value A beside their siblings with it at value B.
 
 usage: tools/resource_usage.py FILE.s [FILE.s ...] --arg INDEX --a A --b B
+       tools/resource_usage.py PARENT.s [PARENT.s ...] --against NEW.s [NEW.s ...]
 
 Per pair one line: the other template arguments, then SGPRs, VGPRs, scratch bytes, static LDS bytes and waves
 per SIMD of the A instantiation and of its B sibling (the "; Kernel info:" block the compiler writes after
 each kernel).  The last line counts the A instantiations with scratch whose B sibling has none; exit status 1
 if there is one.  (The marches' LDS is dynamic -- sized by the host per launch -- so the static figure is 0.)
+
+--against: two builds of the same files instead, each kernel of PARENT.s beside the kernel of the same name and
+template arguments in NEW.s.  The last line counts the kernels with fewer, as many and more waves per SIMD than
+their parent; exit status 1 if a kernel has no partner, one has fewer waves, or one uses scratch.
 """
 import argparse
 import re
@@ -34,13 +39,46 @@ def kernels(path):
     return {k: v for k, v in out.items() if len(v) == len(FIELDS)}
 
 
+def against(parents, news):
+    lower = equal = higher = bad = 0
+    row = "%5d %5d %7d %3d %10d"
+    for pa, pb in zip(parents, news):
+        A, B = kernels(pa), kernels(pb)
+        print("%s | %s" % (pa, pb))
+        print("kernel <template arguments> | parent: SGPRs VGPRs scratch LDS waves/SIMD | new: the same | waves")
+        for k in sorted(A):
+            a, b = A[k], B.get(k)
+            name = "%s<%s>" % (k[0], ", ".join(map(str, k[1])))
+            if b is None:
+                print("%-40s | %s | (no partner)" % (name, row % tuple(a[f] for f in FIELDS)))
+                bad += 1
+                continue
+            d = b["Occupancy"] - a["Occupancy"]
+            lower, equal, higher = lower + (d < 0), equal + (d == 0), higher + (d > 0)
+            bad += b["ScratchSize"] > 0
+            print("%-40s | %s | %s | %s" % (name, row % tuple(a[f] for f in FIELDS), row % tuple(b[f] for f in FIELDS),
+                                           "lower" if d < 0 else "higher" if d > 0 else "equal"))
+        bad += len(set(B) - set(A))
+        print()
+    print("%d kernels: %d with fewer waves per SIMD than their parent, %d with as many, %d with more; "
+          "%d without a partner or with scratch" % (lower + equal + higher, lower, equal, higher, bad))
+    return 1 if lower or bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("files", nargs="+")
-    ap.add_argument("--arg", type=int, required=True, help="index of the template argument that differs")
-    ap.add_argument("--a", type=int, required=True)
-    ap.add_argument("--b", type=int, required=True)
+    ap.add_argument("--against", nargs="+", help="the same files of another build, in the same order")
+    ap.add_argument("--arg", type=int, help="index of the template argument that differs")
+    ap.add_argument("--a", type=int)
+    ap.add_argument("--b", type=int)
     o = ap.parse_args()
+    if o.against:
+        if len(o.against) != len(o.files):
+            ap.error("--against takes as many files as there are ahead of it (%d)" % len(o.files))
+        return against(o.files, o.against)
+    if o.arg is None or o.a is None or o.b is None:
+        ap.error("give --arg, --a and --b, or --against")
     worse = total = 0
     for path in o.files:
         K = kernels(path)

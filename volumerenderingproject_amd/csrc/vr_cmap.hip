@@ -2,9 +2,9 @@
 // classified by a piecewise-linear RGBA colour map (include/vr_api.h, host/colormap.h) instead of
 // the interval transfer function, and the empty-cell bits that follow that map; VR_MODE_SCDVR is the
 // same march with every non-transparent in-volume sample lit and its alpha scaled by the
-// gradient-opacity map G (the kernel's SHADE flag).  Its own translation unit: the sample block of
-// dvr_march_kernel is restated here (as vr_mip.hip and vr_iso.hip do), so vr_dvr.hip's device code
-// stays what it is.
+// gradient-opacity map G (the kernel's SHADE flag).  Its own translation unit and its own kernel (the
+// classification differs from DVR's and neither contains the other); the ray set-up, the inside test,
+// the trilinear sample, the gradient and the headlight are vr_march.h's, shared with DVR, MIP and ISO.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -39,7 +39,7 @@ namespace vr {
 //
 // SHADE (VR_MODE_SCDVR; h is read by these instantiations only): dvr_march_kernel's SHADE -- the
 // headlight per ray, and per sample, once its colour C(v) is known, six more single samples of the
-// field (field_value_at) around the position of a sample in the volume with alpha != 0, the tap loop
+// field (field_gradient) around the position of a sample in the volume with alpha != 0, the tap loop
 // rolled -- and from the central differences len2, mag = sqrtf(len2), the weight G(mag) that scales
 // the sample's alpha and, with len2 > 0 and a light, the normal that goes through shade_normal.  A
 // wave none of whose lanes lights the sample skips all of it.
@@ -57,8 +57,8 @@ namespace vr {
 // scratch left to itself.)
 //
 // CROP (vr_set_crop_box; bx is read by these instantiations only): dvr_march_kernel's CROP -- the
-// effective box in the volume's place in in[k] and in the ESS first-sample test, crop_clip for the ray
-// range; a sample not in the box is C(0.0f), neither lit nor scaled.
+// effective box in the volume's place in in[k] and in the ESS first-sample test (field_inside), crop_clip
+// for the ray range; a sample not in the box is C(0.0f), neither lit nor scaled.
 // ------------------------------------------------------------------------------------------------
 constexpr int kCmapK = 4;
 
@@ -133,37 +133,20 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
     ray_of_thread(wt, x, y);
     if (x >= f.W || y >= f.H) return;
 
-    // TEST's position chain, clip and linear model (vr_march.h)
-    TestRay ray;
-    test_ray_init<LAW>(f, x, y, ray);
-    auto position = [&](int s, float p[3]) { test_position<LAW>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
+    // the ray: TEST's position chain, clip and linear model; SHADE: the headlight from its two end points
+    FieldRay<LAW> R;
     int s_begin, s_end;
-    float pa[3], dp[3], idp[3];
     float L[3] = {0.0f, 0.0f, 0.0f};
     bool lit = false;   // SHADE: the ray has a light direction
     {
         float pb[3];
-        position(0, pa);
-        position(f.S > 1 ? f.S - 1 : 0, pb);
-        if (CROP) crop_clip(f, bx, pa, pb, dp, idp, s_begin, s_end);
-        else test_clip(f, pa, pb, dp, idp, s_begin, s_end);
-        if (SHADE) {   // headlight along the ray, in voxel space (dvr_march_kernel's, from the same two end points)
-            const float ex = pb[0] - pa[0], ey = pb[1] - pa[1], ez = pb[2] - pa[2];
-            const float n2 = (ex * ex + ey * ey) + ez * ez;
-            if (n2 > 0.0f) {
-                const float il = 1.0f / sqrtf(n2);
-                L[0] = -ex * il; L[1] = -ey * il; L[2] = -ez * il;
-                lit = true;
-            }
-        }
+        field_ray_init<LAW, CROP>(f, bx, x, y, s_B, K, R, pb, s_begin, s_end);
+        if (SHADE) lit = headlight(R.pa, pb, L);
     }
 
     const float4 c0 = make_float4(g.c0[0], g.c0[1], g.c0[2], g.c0[3]);
     const int nl = g.n - 1;
-    // (host: the array is addressable with 32-bit byte offsets)
-    const int d3 = (int)f.d3, d23 = (int)(f.d2 * f.d3);
-    const int xl = (int)f.d1 - 1, yl = (int)f.d2 - 1, zl = (int)f.d3 - 1;
-    const __amdgpu_buffer_rsrc_t vrs = uniform_rsrc(vol, g.vol_bytes);
+    const FieldGrid fv = field_grid(f, vol, g.vol_bytes);
     float r, gr, bl, T = 1.0f;
     if (F2B) { r = 0.0f; gr = 0.0f; bl = 0.0f; }
     else { r = f.bg[0]; gr = f.bg[1]; bl = f.bg[2]; }
@@ -173,26 +156,19 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
     float pfirst[3];   // ESS: the position of the batch's first sample, from the empty-cell test
     while (!done) {
         if (ESS) {
-            float* p = pfirst;
-            position(s, p);
-            // (bitwise, not short-circuit: && chains compile to exec-mask branches)
-            bool inside = ((int)(__float_as_uint(p[0]) < __float_as_uint(CROP ? bx.hi[0] : f.fd1)) &
-                           (int)(__float_as_uint(p[1]) < __float_as_uint(CROP ? bx.hi[1] : f.fd2)) &
-                           (int)(__float_as_uint(p[2]) < __float_as_uint(CROP ? bx.hi[2] : f.fd3))) != 0;
-            // CROP: the effective box's upper bounds stand in fd's place; its lower compares (vr_march.h)
-            if (CROP) inside = ((int)inside & (int)crop_lower<CROP>(bx, p[0], p[1], p[2])) != 0;
+            R.position(f, s, pfirst);
+            const bool inside = field_inside<CROP>(f, bx, pfirst[0], pfirst[1], pfirst[2]);
             int cc[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) cc[c] = inside ? ((int)p[c] >> f.tcb) : 0;
-            const int cell = __mul24(__mul24(cc[0], f.tnc[1]) + cc[1], f.tnc[2]) + cc[2];   // (< 2^18 cells)
+            const int cell = field_cell(f, inside, pfirst, cc);
             if (inside && !((occ_word(cell >> 5) >> (cell & 31)) & 1u)) {
-                test_cell_jump<F2B>(f, cc, pa, dp, idp, s_begin, s_end, s, done);
+                test_cell_jump<F2B>(f, cc, R.pa, R.dp, R.idp, s_begin, s_end, s, done);
                 continue;
             }
         }
-        float w[K][3];
-        bool in[K], lastz[K];
-        int off[K][4];
+        // the batch: every position and every gather issued before any is used
+        FieldCorners cs[K];
+        FieldRawA<U8> raw[K];
+        bool in[K];
         bool any_in = false;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -202,78 +178,33 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
             if (ESS && k == 0) {   // (s did not move since the empty-cell test: the same position)
                 p[0] = pfirst[0]; p[1] = pfirst[1]; p[2] = pfirst[2];
             } else {
-                position(sk, p);
+                R.position(f, sk, p);
             }
-            // 0 <= p < fd as unsigned compares of the bits (test_march_kernel)
-            in[k] = ((int)valid & (int)(__float_as_uint(p[0]) < __float_as_uint(CROP ? bx.hi[0] : f.fd1)) &
-                     (int)(__float_as_uint(p[1]) < __float_as_uint(CROP ? bx.hi[1] : f.fd2)) &
-                     (int)(__float_as_uint(p[2]) < __float_as_uint(CROP ? bx.hi[2] : f.fd3))) != 0;
-            if (CROP) in[k] = ((int)in[k] & (int)crop_lower<CROP>(bx, p[0], p[1], p[2])) != 0;
+            in[k] = field_inside<CROP>(f, bx, p[0], p[1], p[2], valid);
             any_in |= in[k];
-            int i0[3];
+            // (field_corners' statements with the three conversions ahead of the fractions, not the call: through
+            // the call <F2B, ESS, float, SMALL, general law, no SHADE, no CROP> takes 97 VGPRs for 96 and goes from
+            // 5 waves per SIMD to 4)
+            const int i0[3] = {(int)p[0], (int)p[1], (int)p[2]};
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                i0[c] = (int)p[c];
-                // p - (float)(int)p: for an in-volume sample (p >= 0) that is p - floor(p), which
-                // v_fract_f32 returns exactly; outside, unused
-                w[k][c] = __builtin_amdgcn_fractf(p[c]);
-            }
-            // corner rows (x, y) at xy = x << 1 | y; the clamp to edge: no step at the last x / y
-            const int base = i0[0] * d23 + i0[1] * d3 + i0[2];
-            const int ox = i0[0] >= xl ? 0 : d23, oy = i0[1] >= yl ? 0 : d3;
-            off[k][0] = base;
-            off[k][1] = base + oy;
-            off[k][2] = base + ox;
-            off[k][3] = base + ox + oy;
-            lastz[k] = i0[2] >= zl;
+            for (int a = 0; a < 3; ++a) cs[k].w[a] = __builtin_amdgcn_fractf(p[a]);
+            const int base = i0[0] * fv.d23 + i0[1] * fv.d3 + i0[2];
+            const int ox = i0[0] >= fv.xl ? 0 : fv.d23, oy = i0[1] >= fv.yl ? 0 : fv.d3;
+            cs[k].off[0] = base;
+            cs[k].off[1] = base + oy;
+            cs[k].off[2] = base + ox;
+            cs[k].off[3] = base + ox + oy;
+            cs[k].lastz = i0[2] >= fv.zl;
         }
-        // the gathers of the whole batch, exec-masked per sample (lanes outside skip them)
-        uint32_t raw[K][U8 ? 4 : 8];
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-            if (in[k]) {
-                if (U8) {
-#pragma unroll
-                    for (int xy = 0; xy < 4; ++xy) raw[k][xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy], 0, 0);
-                } else {
-                    const int zs = lastz[k] ? 0 : 4;
-#pragma unroll
-                    for (int xy = 0; xy < 4; ++xy) {
-                        raw[k][2 * xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4, 0, 0);
-                        raw[k][2 * xy + 1] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4 + zs, 0, 0);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < (U8 ? 4 : 8); ++i) raw[k][i] = 0u;
-            }
-        }
+        for (int k = 0; k < K; ++k) raw[k] = field_gather<U8, FieldRawA<U8>>(fv, in[k], cs[k]);
         // a batch with every lane's samples outside the volume composites C(0) only: with C(0)
         // transparent an exact no-op of either blend (f * (1 - 0) + c * 0 = f, T * (1 - 0) = T)
         const bool blank = f.zero_transparent && !__any(any_in);
         if (!blank) {
 #pragma unroll
             for (int k = 0; k < K; ++k) {
-                float c[8];   // corner kk = x << 2 | y << 1 | z
-#pragma unroll
-                for (int xy = 0; xy < 4; ++xy) {
-                    if (U8) {
-                        const uint32_t z0 = raw[k][xy] & 0xffu, z1 = (raw[k][xy] >> 8) & 0xffu;
-                        c[2 * xy] = (float)z0;
-                        c[2 * xy + 1] = (float)(lastz[k] ? z0 : z1);
-                    } else {
-#pragma unroll
-                        for (int z = 0; z < 2; ++z) {   // a non-finite voxel reads as 0
-                            const uint32_t u = raw[k][2 * xy + z];
-                            c[2 * xy + z] = (u & 0x7f800000u) == 0x7f800000u ? 0.0f : __uint_as_float(u);
-                        }
-                    }
-                }
-                const float dx = w[k][0], dy = w[k][1], dz = w[k][2];
-                const float y1 = lerp1(c[0], c[2], dy), y2 = lerp1(c[1], c[3], dy);
-                const float y3 = lerp1(c[4], c[6], dy), y4 = lerp1(c[5], c[7], dy);
-                const float z1 = lerp1(y1, y3, dx), z2 = lerp1(y2, y4, dx);
-                const float v = lerp1(z1, z2, dz);
+                const float v = field_value<U8>(raw[k], cs[k]);
                 int j = 0;   // the points x_i <= v (a NaN: none)
                 if (SMALL) {
 #pragma unroll
@@ -303,29 +234,10 @@ __global__ __launch_bounds__(256) void cmap_march_kernel(TestFrame f, CmapFrame 
                 const bool sh = SHADE && in[k] && cf.w != 0.0f;
                 if (SHADE && __any(sh)) {
                     float ps[3];
-                    position(sk, ps);   // (the batch kept the sample's fractions only: the same position again)
-                    // gradient of the trilinear field at p: taps t = 2 a (q+) and 2 a + 1 (q-) of axis a, both
-                    // in the volume for a lane that lights (selects, no indexed arrays: the loop is rolled)
-                    float gx = 0.0f, gy = 0.0f, gz = 0.0f, vplus = 0.0f;
-#pragma unroll 1
-                    for (int t = 0; t < 6; ++t) {
-                        const int a = t >> 1;
-                        const float pc = a == 0 ? ps[0] : (a == 1 ? ps[1] : ps[2]);
-                        const float top = (float)(a == 0 ? xl : (a == 1 ? yl : zl));
-                        const float qp = fminf(pc + 1.0f, top), qm = fmaxf(pc - 1.0f, 0.0f);
-                        const float q = (t & 1) ? qm : qp;
-                        const float tv = field_value_at<U8>(sh, a == 0 ? q : ps[0], a == 1 ? q : ps[1],
-                                                            a == 2 ? q : ps[2], vrs, d3, d23, xl, yl, zl);
-                        if (t & 1) {
-                            const float span = qp - qm;
-                            const float ga = span > 0.0f ? (vplus - tv) / span : 0.0f;
-                            gx = a == 0 ? ga : gx;
-                            gy = a == 1 ? ga : gy;
-                            gz = a == 2 ? ga : gz;
-                        } else {
-                            vplus = tv;
-                        }
-                    }
+                    R.position(f, sk, ps);   // (the batch kept the sample's fractions only: the same position again)
+                    // the gradient of the trilinear field at p (six taps, all in the volume for a lane that lights)
+                    float gx, gy, gz;
+                    field_gradient<U8>(sh, ps[0], ps[1], ps[2], fv, gx, gy, gz);
                     const float len2 = (gx * gx + gy * gy) + gz * gz;
                     const float mag = sqrtf(len2);
                     // gradient opacity G(mag), with or without a normal
@@ -432,22 +344,16 @@ hipError_t launch_cmap_march(const TestFrame& f, const CmapFrame& g, const Scdvr
     const size_t lds = cmap_lds_bytes(f, g, ess, shade != nullptr);
     const ScdvrFrame h = shade ? *shade : ScdvrFrame{};
     const CropBox cb = crop ? *crop : CropBox{};
-#define VR_C7(F2B_, ESS_, U8_, SMALL_, LAW_, SHADE_, CROP_)                                                 \
-    hipLaunchKernelGGL((cmap_march_kernel<F2B_, ESS_, U8_, SMALL_, LAW_, SHADE_, CROP_>), dim3(n_blocks),    \
-                       dim3(kWgThreads), lds, st, f, g, h, work, vol, xi, col, occ, out, cb)
-#define VR_C6(F2B_, ESS_, U8_, SMALL_, LAW_, SHADE_) do { if (crop) VR_C7(F2B_, ESS_, U8_, SMALL_, LAW_, SHADE_, true); else VR_C7(F2B_, ESS_, U8_, SMALL_, LAW_, SHADE_, false); } while (0)
-#define VR_C5(F2B_, ESS_, U8_, SMALL_, LAW_) do { if (shade) VR_C6(F2B_, ESS_, U8_, SMALL_, LAW_, true); else VR_C6(F2B_, ESS_, U8_, SMALL_, LAW_, false); } while (0)
-#define VR_C4(F2B_, ESS_, U8_, SMALL_) do { if (f.sep == kLawPersp) VR_C5(F2B_, ESS_, U8_, SMALL_, kLawPersp); else if (f.sep) VR_C5(F2B_, ESS_, U8_, SMALL_, kLawSep); else VR_C5(F2B_, ESS_, U8_, SMALL_, kLawGeneral); } while (0)
-#define VR_C3(F2B_, ESS_, U8_) do { if (small) VR_C4(F2B_, ESS_, U8_, true); else VR_C4(F2B_, ESS_, U8_, false); } while (0)
-#define VR_C2(F2B_, ESS_) do { if (u8) VR_C3(F2B_, ESS_, true); else VR_C3(F2B_, ESS_, false); } while (0)
-    if (f2b) { if (ess) VR_C2(true, true); else VR_C2(true, false); }
-    else { if (ess) VR_C2(false, true); else VR_C2(false, false); }
-#undef VR_C2
-#undef VR_C3
-#undef VR_C4
-#undef VR_C5
-#undef VR_C6
-#undef VR_C7
+    with_flag(f2b, [&](auto F2B) { with_flag(ess, [&](auto ESS) { with_flag(small, [&](auto SMALL) {
+        with_flag(shade != nullptr, [&](auto SHADE) {
+            field_variant(u8, f.sep, crop != nullptr, [&](auto U8, auto LAW, auto CROP) {
+                hipLaunchKernelGGL((cmap_march_kernel<decltype(F2B)::value, decltype(ESS)::value, decltype(U8)::value,
+                                                      decltype(SMALL)::value, decltype(LAW)::value,
+                                                      decltype(SHADE)::value, decltype(CROP)::value>),
+                                   dim3(n_blocks), dim3(kWgThreads), lds, st, f, g, h, work, vol, xi, col, occ, out, cb);
+            });
+        });
+    }); }); });
     return hipGetLastError();
 }
 

@@ -19,7 +19,11 @@ namespace vr {
 // DVR march, one launch per frame, the shape of test_march_kernel: 16 x 16 rays per workgroup (a
 // wave = 8 x 8), work list / background workgroups / hull cull (test_background), TEST's position
 // chain with its per-frame B table in LDS, its linear-model clip and its macro-cell jumps, batches
-// of K = 4 samples whose positions and gathers are all issued before any is used.
+// of K = 4 samples whose positions and gathers are all issued before any is used.  The ray set-up, the
+// inside test, the cell index and the trilinear sample are functions of vr_march.h (field_ray_init,
+// field_inside, field_cell, field_corners / field_gather / field_value), which cmap_march_kernel,
+// mip_march_kernel and iso_march_kernel call too; staging, the ESS decision, classification and blend are
+// this kernel's.
 //
 // Per sample inside the volume (0 <= p_a < d_a): corners i0 = (int)p and i1 = min(i0 + 1, d - 1)
 // (clamp to edge), weights p - (int)p, the 8 voxel values lerped in y, then x, then z (TEST's order,
@@ -43,9 +47,9 @@ namespace vr {
 // (dvr_cells_kernel); skipping them leaves either blend unchanged bit for bit.
 //
 // SHADE (VR_MODE_SDVR; h is read by these instantiations only): per ray the headlight
-// L = -(p(S - 1) - p(0)) / |.|, from the two end points the clip evaluates anyway.  Per sample, once
-// its class is known: the lanes whose sample is in the volume with alpha != 0 run six more single
-// samples of the field (field_value_at) around the sample's position, turn the central differences
+// L = -(p(S - 1) - p(0)) / |.| (headlight), from the two end points the clip evaluates anyway.  Per sample,
+// once its class is known: the lanes whose sample is in the volume with alpha != 0 run six more single
+// samples of the field around the sample's position (field_gradient), turn the central differences
 // into a normal, face it to the light and put the segment's colour through shade_normal before the
 // blend.  The tap loop is rolled (selects, no indexed arrays) so the batch's live gather registers are
 // not multiplied by six, and a wave none of whose lanes shades the sample skips it.  An alpha-0 sample
@@ -133,36 +137,19 @@ __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g,
     ray_of_thread(wt, x, y);
     if (x >= f.W || y >= f.H) return;
 
-    // TEST's position chain, clip and linear model (vr_march.h)
-    TestRay ray;
-    test_ray_init<LAW>(f, x, y, ray);
-    auto position = [&](int s, float p[3]) { test_position<LAW>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
+    // the ray: TEST's position chain, clip and linear model; SHADE: the headlight from its two end points
+    FieldRay<LAW> R;
     int s_begin, s_end;
-    float pa[3], dp[3], idp[3];
     float L[3] = {0.0f, 0.0f, 0.0f};
     bool lit = false;   // SHADE: the ray has a light direction
     {
         float pb[3];
-        position(0, pa);
-        position(f.S > 1 ? f.S - 1 : 0, pb);
-        if (CROP) crop_clip(f, cb, pa, pb, dp, idp, s_begin, s_end);
-        else test_clip(f, pa, pb, dp, idp, s_begin, s_end);
-        if (SHADE) {   // headlight along the ray, in voxel space (iso_march_kernel's, from the same two end points)
-            const float ex = pb[0] - pa[0], ey = pb[1] - pa[1], ez = pb[2] - pa[2];
-            const float n2 = (ex * ex + ey * ey) + ez * ez;
-            if (n2 > 0.0f) {
-                const float il = 1.0f / sqrtf(n2);
-                L[0] = -ex * il; L[1] = -ey * il; L[2] = -ez * il;
-                lit = true;
-            }
-        }
+        field_ray_init<LAW, CROP>(f, cb, x, y, s_B, K, R, pb, s_begin, s_end);
+        if (SHADE) lit = headlight(R.pa, pb, L);
     }
 
     const float4 tf0 = s_seg[g.seg0];
-    // (host: the array is addressable with 32-bit byte offsets)
-    const int d3 = (int)f.d3, d23 = (int)(f.d2 * f.d3);
-    const int xl = (int)f.d1 - 1, yl = (int)f.d2 - 1, zl = (int)f.d3 - 1;
-    const __amdgpu_buffer_rsrc_t vrs = uniform_rsrc(vol, g.vol_bytes);
+    const FieldGrid fv = field_grid(f, vol, g.vol_bytes);
     float r, gr, bl, T = 1.0f;
     if (F2B) { r = 0.0f; gr = 0.0f; bl = 0.0f; }
     else { r = f.bg[0]; gr = f.bg[1]; bl = f.bg[2]; }
@@ -172,26 +159,19 @@ __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g,
     float pfirst[3];   // ESS: the position of the batch's first sample, from the empty-cell test
     while (!done) {
         if (ESS) {
-            float* p = pfirst;
-            position(s, p);
-            // (bitwise, not short-circuit: && chains compile to exec-mask branches)
-            bool inside = ((int)(__float_as_uint(p[0]) < __float_as_uint(CROP ? cb.hi[0] : f.fd1)) &
-                           (int)(__float_as_uint(p[1]) < __float_as_uint(CROP ? cb.hi[1] : f.fd2)) &
-                           (int)(__float_as_uint(p[2]) < __float_as_uint(CROP ? cb.hi[2] : f.fd3))) != 0;
-            // CROP: the effective box's upper bounds stand in fd's place; its lower compares (vr_march.h)
-            if (CROP) inside = ((int)inside & (int)crop_lower<CROP>(cb, p[0], p[1], p[2])) != 0;
+            R.position(f, s, pfirst);
+            const bool inside = field_inside<CROP>(f, cb, pfirst[0], pfirst[1], pfirst[2]);
             int cc[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) cc[c] = inside ? ((int)p[c] >> f.tcb) : 0;
-            const int cell = __mul24(__mul24(cc[0], f.tnc[1]) + cc[1], f.tnc[2]) + cc[2];   // (< 2^18 cells)
+            const int cell = field_cell(f, inside, pfirst, cc);
             if (inside && !((occ_word(cell >> 5) >> (cell & 31)) & 1u)) {
-                test_cell_jump<F2B>(f, cc, pa, dp, idp, s_begin, s_end, s, done);
+                test_cell_jump<F2B>(f, cc, R.pa, R.dp, R.idp, s_begin, s_end, s, done);
                 continue;
             }
         }
-        float w[K][3];
-        bool in[K], lastz[K];
-        int off[K][4];
+        // the batch: every position and every gather issued before any is used
+        FieldCorners cs[K];
+        FieldRawA<U8> raw[K];
+        bool in[K];
         bool any_in = false;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -201,65 +181,30 @@ __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g,
             if (ESS && k == 0) {   // (s did not move since the empty-cell test: the same position)
                 p[0] = pfirst[0]; p[1] = pfirst[1]; p[2] = pfirst[2];
             } else {
-                position(sk, p);
+                R.position(f, sk, p);
             }
-            // 0 <= p < fd as unsigned compares of the bits (test_march_kernel)
-            in[k] = ((int)valid & (int)(__float_as_uint(p[0]) < __float_as_uint(CROP ? cb.hi[0] : f.fd1)) &
-                     (int)(__float_as_uint(p[1]) < __float_as_uint(CROP ? cb.hi[1] : f.fd2)) &
-                     (int)(__float_as_uint(p[2]) < __float_as_uint(CROP ? cb.hi[2] : f.fd3))) != 0;
-            if (CROP) in[k] = ((int)in[k] & (int)crop_lower<CROP>(cb, p[0], p[1], p[2])) != 0;
+            in[k] = field_inside<CROP>(f, cb, p[0], p[1], p[2], valid);
             any_in |= in[k];
-            int i0[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                i0[c] = (int)p[c];
-                // p - (float)(int)p: for an in-volume sample (p >= 0) that is p - floor(p), which
-                // v_fract_f32 returns exactly; outside, unused
-                w[k][c] = __builtin_amdgcn_fractf(p[c]);
-            }
-            // corner rows (x, y) at xy = x << 1 | y; the clamp to edge: no step at the last x / y
-            const int base = i0[0] * d23 + i0[1] * d3 + i0[2];
-            const int ox = i0[0] >= xl ? 0 : d23, oy = i0[1] >= yl ? 0 : d3;
-            off[k][0] = base;
-            off[k][1] = base + oy;
-            off[k][2] = base + ox;
-            off[k][3] = base + ox + oy;
-            lastz[k] = i0[2] >= zl;
+            cs[k] = field_corners(fv, p);
         }
-        // the gathers of the whole batch, exec-masked per sample (lanes outside skip them)
-        uint32_t raw[K][U8 ? 4 : 8];
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-            if (in[k]) {
-                if (U8) {
-#pragma unroll
-                    for (int xy = 0; xy < 4; ++xy) raw[k][xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy], 0, 0);
-                } else {
-                    const int zs = lastz[k] ? 0 : 4;
-#pragma unroll
-                    for (int xy = 0; xy < 4; ++xy) {
-                        raw[k][2 * xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4, 0, 0);
-                        raw[k][2 * xy + 1] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4 + zs, 0, 0);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < (U8 ? 4 : 8); ++i) raw[k][i] = 0u;
-            }
-        }
+        for (int k = 0; k < K; ++k) raw[k] = field_gather<U8, FieldRawA<U8>>(fv, in[k], cs[k]);
         // a batch with every lane's samples outside the volume composites TF(0) only: with TF(0)
         // transparent an exact no-op of either blend (f * (1 - 0) + c * 0 = f, T * (1 - 0) = T)
         const bool blank = f.zero_transparent && !__any(any_in);
         if (!blank) {
 #pragma unroll
             for (int k = 0; k < K; ++k) {
+                // (field_value's statements, not the call: through the call <B2F, no ESS, U8, SEG8, SEP, no SHADE,
+                // CROP> measured above the parent's own range on the half-cut box in four runs of four, 1.005 to
+                // 1.008 of its median, profiles/field_pipeline/probe_ab.txt)
                 float c[8];   // corner kk = x << 2 | y << 1 | z
 #pragma unroll
                 for (int xy = 0; xy < 4; ++xy) {
                     if (U8) {
                         const uint32_t z0 = raw[k][xy] & 0xffu, z1 = (raw[k][xy] >> 8) & 0xffu;
                         c[2 * xy] = (float)z0;
-                        c[2 * xy + 1] = (float)(lastz[k] ? z0 : z1);
+                        c[2 * xy + 1] = (float)(cs[k].lastz ? z0 : z1);
                     } else {
 #pragma unroll
                         for (int z = 0; z < 2; ++z) {   // a non-finite voxel reads as 0
@@ -268,7 +213,7 @@ __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g,
                         }
                     }
                 }
-                const float dx = w[k][0], dy = w[k][1], dz = w[k][2];
+                const float dx = cs[k].w[0], dy = cs[k].w[1], dz = cs[k].w[2];
                 const float y1 = lerp1(c[0], c[2], dy), y2 = lerp1(c[1], c[3], dy);
                 const float y3 = lerp1(c[4], c[6], dy), y4 = lerp1(c[5], c[7], dy);
                 const float z1 = lerp1(y1, y3, dx), z2 = lerp1(y2, y4, dx);
@@ -293,29 +238,10 @@ __global__ __launch_bounds__(256) void dvr_march_kernel(TestFrame f, DvrFrame g,
                 const bool sh = SHADE && in[k] && cf.w != 0.0f;
                 if (SHADE && __any(sh)) {
                     float ps[3];
-                    position(sk, ps);   // (the batch kept the sample's fractions only: the same position again)
-                    // gradient of the trilinear field at p: taps t = 2 a (q+) and 2 a + 1 (q-) of axis a, both
-                    // in the volume for a lane that shades (selects, no indexed arrays: the loop is rolled)
-                    float gx = 0.0f, gy = 0.0f, gz = 0.0f, vplus = 0.0f;
-#pragma unroll 1
-                    for (int t = 0; t < 6; ++t) {
-                        const int a = t >> 1;
-                        const float pc = a == 0 ? ps[0] : (a == 1 ? ps[1] : ps[2]);
-                        const float top = (float)(a == 0 ? xl : (a == 1 ? yl : zl));
-                        const float qp = fminf(pc + 1.0f, top), qm = fmaxf(pc - 1.0f, 0.0f);
-                        const float q = (t & 1) ? qm : qp;
-                        const float tv = field_value_at<U8>(sh, a == 0 ? q : ps[0], a == 1 ? q : ps[1],
-                                                            a == 2 ? q : ps[2], vrs, d3, d23, xl, yl, zl);
-                        if (t & 1) {
-                            const float span = qp - qm;
-                            const float ga = span > 0.0f ? (vplus - tv) / span : 0.0f;
-                            gx = a == 0 ? ga : gx;
-                            gy = a == 1 ? ga : gy;
-                            gz = a == 2 ? ga : gz;
-                        } else {
-                            vplus = tv;
-                        }
-                    }
+                    R.position(f, sk, ps);   // (the batch kept the sample's fractions only: the same position again)
+                    // the gradient of the trilinear field at p (six taps, all in the volume for a lane that shades)
+                    float gx, gy, gz;
+                    field_gradient<U8>(sh, ps[0], ps[1], ps[2], fv, gx, gy, gz);
                     const float len2 = (gx * gx + gy * gy) + gz * gz;
                     float4 nv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                     if (lit && len2 > 0.0f) {   // (without a light direction: d = 1, spec = 0, as without a normal)
@@ -450,22 +376,17 @@ hipError_t launch_dvr_march(const TestFrame& f, const DvrFrame& g, const SdvrFra
     const size_t lds = dvr_lds_bytes(f, g, ess);
     const SdvrFrame h = shade ? *shade : SdvrFrame{};
     const CropBox cb = crop ? *crop : CropBox{};
-#define VR_D7(F2B_, ESS_, U8_, SEG8_, LAW_, SHADE_, CROP_)                                                  \
-    hipLaunchKernelGGL((dvr_march_kernel<F2B_, ESS_, U8_, SEG8_, LAW_, SHADE_, CROP_>), dim3(n_blocks),      \
-                       dim3(kWgThreads), lds, st, f, g, h, work, vol, start, seg, occ, out, cb)
-#define VR_D6(F2B_, ESS_, U8_, SEG8_, LAW_, SHADE_) do { if (crop) VR_D7(F2B_, ESS_, U8_, SEG8_, LAW_, SHADE_, true); else VR_D7(F2B_, ESS_, U8_, SEG8_, LAW_, SHADE_, false); } while (0)
-#define VR_D5(F2B_, ESS_, U8_, SEG8_, LAW_) do { if (shade) VR_D6(F2B_, ESS_, U8_, SEG8_, LAW_, true); else VR_D6(F2B_, ESS_, U8_, SEG8_, LAW_, false); } while (0)
-#define VR_D4(F2B_, ESS_, U8_, SEG8_) do { if (f.sep == kLawPersp) VR_D5(F2B_, ESS_, U8_, SEG8_, kLawPersp); else if (f.sep) VR_D5(F2B_, ESS_, U8_, SEG8_, kLawSep); else VR_D5(F2B_, ESS_, U8_, SEG8_, kLawGeneral); } while (0)
-#define VR_D3(F2B_, ESS_, U8_) do { if (seg8) VR_D4(F2B_, ESS_, U8_, true); else VR_D4(F2B_, ESS_, U8_, false); } while (0)
-#define VR_D2(F2B_, ESS_) do { if (u8) VR_D3(F2B_, ESS_, true); else VR_D3(F2B_, ESS_, false); } while (0)
-    if (f2b) { if (ess) VR_D2(true, true); else VR_D2(true, false); }
-    else { if (ess) VR_D2(false, true); else VR_D2(false, false); }
-#undef VR_D2
-#undef VR_D3
-#undef VR_D4
-#undef VR_D5
-#undef VR_D6
-#undef VR_D7
+    with_flag(f2b, [&](auto F2B) { with_flag(ess, [&](auto ESS) { with_flag(seg8, [&](auto SEG8) {
+        with_flag(shade != nullptr, [&](auto SHADE) {
+            field_variant(u8, f.sep, crop != nullptr, [&](auto U8, auto LAW, auto CROP) {
+                hipLaunchKernelGGL((dvr_march_kernel<decltype(F2B)::value, decltype(ESS)::value, decltype(U8)::value,
+                                                     decltype(SEG8)::value, decltype(LAW)::value,
+                                                     decltype(SHADE)::value, decltype(CROP)::value>),
+                                   dim3(n_blocks), dim3(kWgThreads), lds, st, f, g, h, work, vol, start, seg, occ, out,
+                                   cb);
+            });
+        });
+    }); }); });
     return hipGetLastError();
 }
 

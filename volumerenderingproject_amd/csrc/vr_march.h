@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "vr_device.h"
 
 namespace vr {
@@ -229,11 +231,10 @@ __device__ __forceinline__ void test_position(const TestFrame& f, const TestRay&
 // one gives an infinite reciprocal, whose products keep the test conservative (a NaN from 0 * inf
 // is ignored by fminf / fmaxf: no constraint).  PERSP: p(s) is affine in s in real arithmetic too (t and
 // B are), and its two more roundings (t, A_r * t) are again ulps of |p|: the same margins hold.
-__device__ __forceinline__ void test_clip(const TestFrame& f, const float pa[3], const float pb[3], float dp[3],
-                                          float idp[3], int& s_begin, int& s_end) {
+__device__ __forceinline__ void box_clip(const TestFrame& f, const float blo[3], const float bhi[3], const float pa[3],
+                                         const float pb[3], float dp[3], float idp[3], int& s_begin, int& s_end) {
     s_begin = 0;
     s_end = f.S;
-    const float dims[3] = {f.fd1, f.fd2, f.fd3};
     const float den = (float)(f.S > 1 ? f.S - 1 : 1);
     float a = 0.0f, bnd = (float)(f.S - 1);
     bool off = false;
@@ -241,7 +242,7 @@ __device__ __forceinline__ void test_clip(const TestFrame& f, const float pa[3],
     for (int c = 0; c < 3; ++c) {
         dp[c] = f.S > 1 ? (pb[c] - pa[c]) / den : 0.0f;
         idp[c] = dp[c] != 0.0f ? 1.0f / dp[c] : 0.0f;
-        const float lo = -0.01f, hi = dims[c] + 0.01f;
+        const float lo = blo[c] - 0.01f, hi = bhi[c] + 0.01f;
         if (dp[c] == 0.0f) {
             off |= (pa[c] < lo) | (pa[c] > hi);
         } else {
@@ -258,6 +259,12 @@ __device__ __forceinline__ void test_clip(const TestFrame& f, const float pa[3],
             s_end = min(f.S, (int)ceilf(bnd) + 2);
         }
     }
+}
+// the volume [0, d) as the box (the constant zeros fold: 0 - 0.01f is the literal)
+__device__ __forceinline__ void test_clip(const TestFrame& f, const float pa[3], const float pb[3], float dp[3],
+                                          float idp[3], int& s_begin, int& s_end) {
+    const float zero[3] = {0.0f, 0.0f, 0.0f}, dims[3] = {f.fd1, f.fd2, f.fd3};
+    box_clip(f, zero, dims, pa, pb, dp, idp, s_begin, s_end);
 }
 
 // The crop box (vr_set_crop_box; the CROP instantiations of the field marches).  cb is the effective box
@@ -279,32 +286,70 @@ __device__ __forceinline__ bool crop_lower(const CropBox& cb, float px, float py
 // E: not in the box, or not in the volume.
 __device__ __forceinline__ void crop_clip(const TestFrame& f, const CropBox& cb, const float pa[3], const float pb[3],
                                           float dp[3], float idp[3], int& s_begin, int& s_end) {
-    s_begin = 0;
-    s_end = f.S;
-    const float den = (float)(f.S > 1 ? f.S - 1 : 1);
-    float a = 0.0f, bnd = (float)(f.S - 1);
-    bool off = false;
+    box_clip(f, cb.lo, cb.hi, pa, pb, dp, idp, s_begin, s_end);
+}
+
+// "In the volume", or CROP "in the volume and in the box", at every use of the field marches (a sample of
+// the batch, the ESS first-sample test, ISO's bisection): 0 <= p < fd per axis as unsigned compares of the
+// bits (test_march_kernel), the effective box's upper bounds in fd's place and its lower compares.
+// (Bitwise, not short-circuit: && chains compile to exec-mask branches.)  valid: a sample's range test at
+// the head of the chain, where dvr_march_kernel and cmap_march_kernel have it; MIP and ISO AND it on
+// outside, as each did before -- either association the other way costs instantiations a wave
+// (profiles/field_pipeline/).
+template <bool CROP>
+__device__ __forceinline__ bool field_inside(const TestFrame& f, const CropBox& cb, float px, float py, float pz,
+                                             bool valid = true) {
+    bool in = ((int)valid & (int)(__float_as_uint(px) < __float_as_uint(CROP ? cb.hi[0] : f.fd1)) &
+               (int)(__float_as_uint(py) < __float_as_uint(CROP ? cb.hi[1] : f.fd2)) &
+               (int)(__float_as_uint(pz) < __float_as_uint(CROP ? cb.hi[2] : f.fd3))) != 0;
+    if (CROP) in = ((int)in & (int)crop_lower<CROP>(cb, px, py, pz)) != 0;
+    return in;
+}
+
+// ESS: the macro cell cc (2^tcb voxels per axis) of a position and its index in the cell arrays (< 2^18
+// cells); a lane outside has cell 0, so a load with the index is in range (and unused)
+__device__ __forceinline__ int field_cell(const TestFrame& f, bool inside, const float p[3], int cc[3]) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        dp[c] = f.S > 1 ? (pb[c] - pa[c]) / den : 0.0f;
-        idp[c] = dp[c] != 0.0f ? 1.0f / dp[c] : 0.0f;
-        const float lo = cb.lo[c] - 0.01f, hi = cb.hi[c] + 0.01f;
-        if (dp[c] == 0.0f) {
-            off |= (pa[c] < lo) | (pa[c] > hi);
-        } else {
-            const float t0 = (lo - pa[c]) * idp[c], t1 = (hi - pa[c]) * idp[c];
-            a = fmaxf(a, fminf(t0, t1));
-            bnd = fminf(bnd, fmaxf(t0, t1));
-        }
+    for (int c = 0; c < 3; ++c) cc[c] = inside ? ((int)p[c] >> f.tcb) : 0;
+    return __mul24(__mul24(cc[0], f.tnc[1]) + cc[1], f.tnc[2]) + cc[2];
+}
+
+// A ray of a field march: TEST's position chain (with the workgroup's B table, built for batches of K), the
+// exact end points pa = p(0) and pb = p(S - 1), the linear model and the sample range clipped to the
+// volume, or CROP to the box.
+template <int LAW>
+struct FieldRay {
+    TestRay ray;
+    const float4* s_B;
+    int K;
+    float pa[3], dp[3], idp[3];
+    __device__ __forceinline__ void position(const TestFrame& f, int s, float p[3]) const {
+        test_position<LAW>(f, ray, s_B, f.sep_tab != 0, K, s, p);
     }
-    if (f.zero_transparent) {
-        if (off || !(a <= bnd)) {
-            s_end = 0;
-        } else {
-            s_begin = max(0, (int)floorf(a) - 1);
-            s_end = min(f.S, (int)ceilf(bnd) + 2);
-        }
+};
+template <int LAW, bool CROP>
+__device__ __forceinline__ void field_ray_init(const TestFrame& f, const CropBox& cb, int x, int y, const float4* s_B,
+                                               int K, FieldRay<LAW>& R, float pb[3], int& s_begin, int& s_end) {
+    R.s_B = s_B;
+    R.K = K;
+    test_ray_init<LAW>(f, x, y, R.ray);
+    R.position(f, 0, R.pa);
+    R.position(f, f.S > 1 ? f.S - 1 : 0, pb);
+    if (CROP) crop_clip(f, cb, R.pa, pb, R.dp, R.idp, s_begin, s_end);
+    else test_clip(f, R.pa, pb, R.dp, R.idp, s_begin, s_end);
+}
+
+// The headlight of the shaded marches, along the ray in voxel space: L = -(pb - pa) / |pb - pa| from two
+// points of the ray; false (and L = 0) when they coincide -- no light direction: d = 1, spec = 0
+__device__ __forceinline__ bool headlight(const float pa[3], const float pb[3], float L[3]) {
+    const float ex = pb[0] - pa[0], ey = pb[1] - pa[1], ez = pb[2] - pa[2];
+    const float n2 = (ex * ex + ey * ey) + ez * ez;
+    L[0] = 0.0f; L[1] = 0.0f; L[2] = 0.0f;
+    if (n2 > 0.0f) {
+        const float il = 1.0f / sqrtf(n2);
+        L[0] = -ex * il; L[1] = -ey * il; L[2] = -ez * il;
     }
+    return n2 > 0.0f;
 }
 
 // ESS: sample s lies in the empty macro cell cc (2^tcb voxels per axis): the next sample in march
@@ -345,47 +390,99 @@ __device__ __forceinline__ float lerp1(float a, float b, float w) {
     return a * u + b * w;
 }
 
-// One sample of the field at a point inside the volume (ISO's bisection and gradient taps, the gradient
-// taps of the DVR and CDVR marches' SHADE variants): corners (int)p and min((int)p + 1, d - 1), weights
-// p - (int)p, the gathers of the march (U8: four unaligned dwords of the byte copy; else eight float
-// gathers, a non-finite voxel reading as 0; the edge clamp by selects), lerp1 in y, x, z.  Lanes with
-// ok false issue no load and return 0.
-template <bool U8>
-__device__ __forceinline__ float field_value_at(bool ok, float px, float py, float pz, __amdgpu_buffer_rsrc_t vrs,
-                                                int d3, int d23, int xl, int yl, int zl) {
-    const int ix = (int)px, iy = (int)py, iz = (int)pz;
-    const float dx = __builtin_amdgcn_fractf(px), dy = __builtin_amdgcn_fractf(py), dz = __builtin_amdgcn_fractf(pz);
-    const int base = ix * d23 + iy * d3 + iz;
-    const int ox = ix >= xl ? 0 : d23, oy = iy >= yl ? 0 : d3;
-    const bool lastz = iz >= zl;
-    int off[4];
-    off[0] = base;
-    off[1] = base + oy;
-    off[2] = base + ox;
-    off[3] = base + ox + oy;
-    uint32_t raw[U8 ? 4 : 8];
+// ------------------------------------------------------------------------------------------------
+// The trilinear sample of the scalar field, one text for the four field marches' batches (DVR, CDVR, MIP,
+// ISO: field_corners per sample, then field_gather of the whole batch, then field_value) and for the
+// single samples (field_value_at: ISO's bisection, the gradient taps).  ISO's hit test and its bisection
+// meet at the same points and agree bit for bit because they are these same functions.
+// ------------------------------------------------------------------------------------------------
+// The volume as the sample addresses it (host: the array is addressable with 32-bit byte offsets)
+struct FieldGrid {
+    __amdgpu_buffer_rsrc_t rs;
+    int d3, d23, xl, yl, zl;   // row and slab strides, the last index per axis
+};
+__device__ __forceinline__ FieldGrid field_grid(const TestFrame& f, const void* vol, int vol_bytes) {
+    FieldGrid v;
+    v.d3 = (int)f.d3; v.d23 = (int)(f.d2 * f.d3);
+    v.xl = (int)f.d1 - 1; v.yl = (int)f.d2 - 1; v.zl = (int)f.d3 - 1;
+    v.rs = uniform_rsrc(vol, vol_bytes);
+    return v;
+}
+
+// A sample's corners (int)p and min((int)p + 1, d - 1) and its weights
+struct FieldCorners {
+    float w[3];
+    int off[4];   // corner rows (x, y) at xy = x << 1 | y, voxel offsets of their z0
+    bool lastz;
+};
+__device__ __forceinline__ FieldCorners field_corners(const FieldGrid& fv, const float p[3]) {
+    FieldCorners c;
+    int i0[3];
 #pragma unroll
-    for (int i = 0; i < (U8 ? 4 : 8); ++i) raw[i] = 0u;
+    for (int a = 0; a < 3; ++a) {
+        i0[a] = (int)p[a];
+        // p - (float)(int)p: for an in-volume sample (p >= 0) that is p - floor(p), which
+        // v_fract_f32 returns exactly; outside, unused
+        c.w[a] = __builtin_amdgcn_fractf(p[a]);
+    }
+    // the clamp to edge: no step at the last x / y
+    const int base = i0[0] * fv.d23 + i0[1] * fv.d3 + i0[2];
+    const int ox = i0[0] >= fv.xl ? 0 : fv.d23, oy = i0[1] >= fv.yl ? 0 : fv.d3;
+    c.off[0] = base;
+    c.off[1] = base + oy;
+    c.off[2] = base + ox;
+    c.off[3] = base + ox + oy;
+    c.lastz = i0[2] >= fv.zl;
+    return c;
+}
+
+// The gathers of a sample, exec-masked (lanes with ok false issue no load and hold zeros).  U8: four
+// unaligned dwords of the byte copy, the z0 and z0 + 1 voxels in the low two bytes; else eight float
+// gathers, the z clamp in the offset.  RAW holds the dwords: a vector for the single sample (FieldRaw: the
+// compiler keeps one 8-wide phi across the exec mask, as it did for field_value_at's own array) and an array
+// for the samples of a batch (FieldRawA).  One text, two containers: the vector in the batches costs three DVR
+// instantiations a wave (72 -> 74 VGPRs), the array in the single sample four shaded ones (94 -> 98).
+template <bool U8> struct FieldRawV { typedef uint32_t type __attribute__((ext_vector_type(U8 ? 4 : 8))); };
+template <bool U8> using FieldRaw = typename FieldRawV<U8>::type;
+template <bool U8> struct FieldRawA {
+    uint32_t u[U8 ? 4 : 8];
+    __device__ __forceinline__ uint32_t& operator[](int i) { return u[i]; }
+    __device__ __forceinline__ uint32_t operator[](int i) const { return u[i]; }
+};
+template <bool U8, class RAW = FieldRaw<U8>>
+__device__ __forceinline__ RAW field_gather(const FieldGrid& fv, bool ok, const FieldCorners& c) {
+    RAW raw;
     if (ok) {
         if (U8) {
 #pragma unroll
-            for (int xy = 0; xy < 4; ++xy) raw[xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy], 0, 0);
+            for (int xy = 0; xy < 4; ++xy) raw[xy] = __builtin_amdgcn_raw_buffer_load_b32(fv.rs, c.off[xy], 0, 0);
         } else {
-            const int zs = lastz ? 0 : 4;
+            const int zs = c.lastz ? 0 : 4;
 #pragma unroll
             for (int xy = 0; xy < 4; ++xy) {
-                raw[2 * xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy] * 4, 0, 0);
-                raw[2 * xy + 1] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[xy] * 4 + zs, 0, 0);
+                raw[2 * xy] = __builtin_amdgcn_raw_buffer_load_b32(fv.rs, c.off[xy] * 4, 0, 0);
+                raw[2 * xy + 1] = __builtin_amdgcn_raw_buffer_load_b32(fv.rs, c.off[xy] * 4 + zs, 0, 0);
             }
         }
+    } else {
+#pragma unroll
+        for (int i = 0; i < (U8 ? 4 : 8); ++i) raw[i] = 0u;
     }
+    return raw;
+}
+
+// The value from the gathers: the corners decoded (U8: the byte unpack and the z clamp by a select; else a
+// non-finite voxel reads as 0), lerp1 in y, x, z
+template <bool U8, class RAW>
+__device__ __forceinline__ float field_value(const RAW& raw, const FieldCorners& cs) {
+    const float dx = cs.w[0], dy = cs.w[1], dz = cs.w[2];
     float c[8];   // corner kk = x << 2 | y << 1 | z
 #pragma unroll
     for (int xy = 0; xy < 4; ++xy) {
         if (U8) {
             const uint32_t z0 = raw[xy] & 0xffu, z1 = (raw[xy] >> 8) & 0xffu;
             c[2 * xy] = (float)z0;
-            c[2 * xy + 1] = (float)(lastz ? z0 : z1);
+            c[2 * xy + 1] = (float)(cs.lastz ? z0 : z1);
         } else {
 #pragma unroll
             for (int z = 0; z < 2; ++z) {   // a non-finite voxel reads as 0
@@ -398,6 +495,44 @@ __device__ __forceinline__ float field_value_at(bool ok, float px, float py, flo
     const float y3 = lerp1(c[4], c[6], dy), y4 = lerp1(c[5], c[7], dy);
     const float z1 = lerp1(y1, y3, dx), z2 = lerp1(y2, y4, dx);
     return lerp1(z1, z2, dz);
+}
+
+// One sample of the field at a point inside the volume; lanes with ok false issue no load and return 0
+template <bool U8>
+__device__ __forceinline__ float field_value_at(bool ok, float px, float py, float pz, const FieldGrid& fv) {
+    const float p[3] = {px, py, pz};
+    const FieldCorners c = field_corners(fv, p);
+    return field_value<U8>(field_gather<U8>(fv, ok, c), c);
+}
+
+// The gradient of the trilinear field at (px, py, pz) by central differences: taps t = 2 a (q+) and 2 a + 1 (q-) of
+// axis a, one voxel either way clamped to the volume (both in it for a lane with ok; the others issue no
+// load).  Selects on values, no indexed arrays (the point and fv by value: a select between elements reached
+// through a pointer turns into an indexed read of the caller's array, which then lives in scratch), and the
+// loop rolled: six single samples' registers are not live at once.
+template <bool U8>
+__device__ __forceinline__ void field_gradient(bool ok, float px, float py, float pz, const FieldGrid fv, float& gx,
+                                               float& gy, float& gz) {
+    float vplus = 0.0f;
+    gx = 0.0f; gy = 0.0f; gz = 0.0f;
+#pragma unroll 1
+    for (int t = 0; t < 6; ++t) {
+        const int a = t >> 1;
+        const float pc = a == 0 ? px : (a == 1 ? py : pz);
+        const float top = (float)(a == 0 ? fv.xl : (a == 1 ? fv.yl : fv.zl));
+        const float qp = fminf(pc + 1.0f, top), qm = fmaxf(pc - 1.0f, 0.0f);
+        const float q = (t & 1) ? qm : qp;
+        const float tv = field_value_at<U8>(ok, a == 0 ? q : px, a == 1 ? q : py, a == 2 ? q : pz, fv);
+        if (t & 1) {
+            const float span = qp - qm;
+            const float ga = span > 0.0f ? (vplus - tv) / span : 0.0f;
+            gx = a == 0 ? ga : gx;
+            gy = a == 1 ? ga : gy;
+            gz = a == 2 ? ga : gz;
+        } else {
+            vplus = tv;
+        }
+    }
 }
 
 // Headlight Phong at a sample (oracle or_shade: same operations, same order):
@@ -466,6 +601,27 @@ __device__ __forceinline__ void count_work(unsigned long long* stats, unsigned g
     if (gathers) atomicAdd(stats, (unsigned long long)gathers);
     if (samples) atomicAdd(stats + 1, (unsigned long long)samples);
     if (bytes) atomicAdd(stats + 2, (unsigned long long)bytes);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host: from run-time flags to template arguments.  with_flag calls fn with std::true_type or
+// std::false_type; field_variant walks the rungs every field march's launch ladder shares -- the byte
+// copy, the position law (TestFrame.sep) and the crop box -- and calls fn(U8, LAW, CROP) with integral
+// constants.  A launch wrapper adds its own rungs around it.
+// ------------------------------------------------------------------------------------------------
+template <class F>
+inline void with_flag(bool on, F&& fn) {
+    if (on) fn(std::true_type{}); else fn(std::false_type{});
+}
+template <class F>
+inline void field_variant(bool u8, int law, bool crop, F&& fn) {
+    with_flag(u8, [&](auto U8) {
+        with_flag(crop, [&](auto CROP) {
+            if (law == kLawPersp) fn(U8, std::integral_constant<int, kLawPersp>{}, CROP);
+            else if (law) fn(U8, std::integral_constant<int, kLawSep>{}, CROP);
+            else fn(U8, std::integral_constant<int, kLawGeneral>{}, CROP);
+        });
+    });
 }
 
 }  // namespace vr

@@ -17,7 +17,8 @@ namespace vr {
 // chain with its per-frame B table in LDS, its linear-model clip and its macro-cell jumps, batches
 // of K = 4 samples whose positions and gathers are all issued before any is used.
 //
-// Per sample inside the volume (0 <= p_a < d_a) the value v is DVR's, operation for operation:
+// Per sample inside the volume (0 <= p_a < d_a) the value v is DVR's -- the same functions, vr_march.h's
+// field_corners, field_gather and field_value:
 // corners (int)p and min((int)p + 1, d - 1), weights p - (int)p, the 8 voxel values (U8: four
 // unaligned dwords of the byte copy, the edge clamp by selects; else eight clamped float gathers, a
 // non-finite voxel reading as 0) lerped in y, then x, then z by lerp1.  Per lane the running maximum
@@ -67,25 +68,15 @@ __global__ __launch_bounds__(256) void mip_march_kernel(TestFrame f, MipFrame g,
     ray_of_thread(wt, x, y);
     if (x >= f.W || y >= f.H) return;
 
-    // TEST's position chain, clip and linear model (vr_march.h)
-    TestRay ray;
-    test_ray_init<LAW>(f, x, y, ray);
-    auto position = [&](int s, float p[3]) { test_position<LAW>(f, ray, s_B, f.sep_tab != 0, K, s, p); };
+    // the ray: TEST's position chain, clip and linear model (host: zero_transparent = 1, the clip always holds)
+    FieldRay<LAW> R;
     int s_begin, s_end;
-    float pa[3], dp[3], idp[3];
     {
         float pb[3];
-        position(0, pa);
-        position(f.S > 1 ? f.S - 1 : 0, pb);
-        // (host: zero_transparent = 1, the clip always holds)
-        if (CROP) crop_clip(f, cb, pa, pb, dp, idp, s_begin, s_end);
-        else test_clip(f, pa, pb, dp, idp, s_begin, s_end);
+        field_ray_init<LAW, CROP>(f, cb, x, y, s_B, K, R, pb, s_begin, s_end);
     }
 
-    // (host: the array is addressable with 32-bit byte offsets)
-    const int d3 = (int)f.d3, d23 = (int)(f.d2 * f.d3);
-    const int xl = (int)f.d1 - 1, yl = (int)f.d2 - 1, zl = (int)f.d3 - 1;
-    const __amdgpu_buffer_rsrc_t vrs = uniform_rsrc(vol, g.vol_bytes);
+    const FieldGrid fv = field_grid(f, vol, g.vol_bytes);
     const __amdgpu_buffer_rsrc_t brs = uniform_rsrc(gbound, ESS ? g.bound_bytes : 0);
     // ERT: nothing exceeds the volume's largest bound (without the flag: only m = +inf stops)
     const float stop = (f.flags & 2) ? g.vol_bound : __builtin_inff();
@@ -97,27 +88,20 @@ __global__ __launch_bounds__(256) void mip_march_kernel(TestFrame f, MipFrame g,
     float pfirst[3];   // ESS: the position of the batch's first sample, from the cell test
     while (!done) {
         if (ESS) {
-            float* p = pfirst;
-            position(s, p);
-            // (bitwise, not short-circuit: && chains compile to exec-mask branches)
-            bool inside = ((int)(__float_as_uint(p[0]) < __float_as_uint(CROP ? cb.hi[0] : f.fd1)) &
-                           (int)(__float_as_uint(p[1]) < __float_as_uint(CROP ? cb.hi[1] : f.fd2)) &
-                           (int)(__float_as_uint(p[2]) < __float_as_uint(CROP ? cb.hi[2] : f.fd3))) != 0;
-            // CROP: the effective box's upper bounds stand in fd's place; its lower compares (vr_march.h)
-            if (CROP) inside = ((int)inside & (int)crop_lower<CROP>(cb, p[0], p[1], p[2])) != 0;
+            R.position(f, s, pfirst);
+            const bool inside = field_inside<CROP>(f, cb, pfirst[0], pfirst[1], pfirst[2]);
             int cc[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) cc[c] = inside ? ((int)p[c] >> f.tcb) : 0;
-            const int cell = __mul24(__mul24(cc[0], f.tnc[1]) + cc[1], f.tnc[2]) + cc[2];   // (< 2^18 cells)
+            const int cell = field_cell(f, inside, pfirst, cc);
             const float bound = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(brs, cell * 4, 0, 0));
             if (inside && bound <= m) {   // (m = -inf before the ray's first sample: never)
-                test_cell_jump<true>(f, cc, pa, dp, idp, s_begin, s_end, s, done);
+                test_cell_jump<true>(f, cc, R.pa, R.dp, R.idp, s_begin, s_end, s, done);
                 continue;
             }
         }
-        float w[K][3];
-        bool in[K], lastz[K];
-        int off[K][4];
+        // the batch: every position and every gather issued before any is used
+        FieldCorners cs[K];
+        FieldRawA<U8> raw[K];
+        bool in[K];
         bool any_in = false;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -126,75 +110,18 @@ __global__ __launch_bounds__(256) void mip_march_kernel(TestFrame f, MipFrame g,
             if (ESS && k == 0) {   // (s did not move since the cell test: the same position)
                 p[0] = pfirst[0]; p[1] = pfirst[1]; p[2] = pfirst[2];
             } else {
-                position(sk, p);
+                R.position(f, sk, p);
             }
-            // 0 <= p < fd as unsigned compares of the bits (test_march_kernel)
-            in[k] = ((int)(sk < s_end) & (int)(__float_as_uint(p[0]) < __float_as_uint(CROP ? cb.hi[0] : f.fd1)) &
-                     (int)(__float_as_uint(p[1]) < __float_as_uint(CROP ? cb.hi[1] : f.fd2)) &
-                     (int)(__float_as_uint(p[2]) < __float_as_uint(CROP ? cb.hi[2] : f.fd3))) != 0;
-            if (CROP) in[k] = ((int)in[k] & (int)crop_lower<CROP>(cb, p[0], p[1], p[2])) != 0;
+            in[k] = ((int)(sk < s_end) & (int)field_inside<CROP>(f, cb, p[0], p[1], p[2])) != 0;
             any_in |= in[k];
-            int i0[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                i0[c] = (int)p[c];
-                // p - (float)(int)p: for an in-volume sample (p >= 0) that is p - floor(p), which
-                // v_fract_f32 returns exactly; outside, unused
-                w[k][c] = __builtin_amdgcn_fractf(p[c]);
-            }
-            // corner rows (x, y) at xy = x << 1 | y; the clamp to edge: no step at the last x / y
-            const int base = i0[0] * d23 + i0[1] * d3 + i0[2];
-            const int ox = i0[0] >= xl ? 0 : d23, oy = i0[1] >= yl ? 0 : d3;
-            off[k][0] = base;
-            off[k][1] = base + oy;
-            off[k][2] = base + ox;
-            off[k][3] = base + ox + oy;
-            lastz[k] = i0[2] >= zl;
+            cs[k] = field_corners(fv, p);
         }
-        // the gathers of the whole batch, exec-masked per sample (lanes outside skip them)
-        uint32_t raw[K][U8 ? 4 : 8];
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-            if (in[k]) {
-                if (U8) {
-#pragma unroll
-                    for (int xy = 0; xy < 4; ++xy) raw[k][xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy], 0, 0);
-                } else {
-                    const int zs = lastz[k] ? 0 : 4;
-#pragma unroll
-                    for (int xy = 0; xy < 4; ++xy) {
-                        raw[k][2 * xy] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4, 0, 0);
-                        raw[k][2 * xy + 1] = __builtin_amdgcn_raw_buffer_load_b32(vrs, off[k][xy] * 4 + zs, 0, 0);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < (U8 ? 4 : 8); ++i) raw[k][i] = 0u;
-            }
-        }
+        for (int k = 0; k < K; ++k) raw[k] = field_gather<U8, FieldRawA<U8>>(fv, in[k], cs[k]);
         if (__any(any_in)) {   // (a batch with every lane's samples outside the volume changes nothing)
 #pragma unroll
             for (int k = 0; k < K; ++k) {
-                float c[8];   // corner kk = x << 2 | y << 1 | z
-#pragma unroll
-                for (int xy = 0; xy < 4; ++xy) {
-                    if (U8) {
-                        const uint32_t z0 = raw[k][xy] & 0xffu, z1 = (raw[k][xy] >> 8) & 0xffu;
-                        c[2 * xy] = (float)z0;
-                        c[2 * xy + 1] = (float)(lastz[k] ? z0 : z1);
-                    } else {
-#pragma unroll
-                        for (int z = 0; z < 2; ++z) {   // a non-finite voxel reads as 0
-                            const uint32_t u = raw[k][2 * xy + z];
-                            c[2 * xy + z] = (u & 0x7f800000u) == 0x7f800000u ? 0.0f : __uint_as_float(u);
-                        }
-                    }
-                }
-                const float dx = w[k][0], dy = w[k][1], dz = w[k][2];
-                const float y1 = lerp1(c[0], c[2], dy), y2 = lerp1(c[1], c[3], dy);
-                const float y3 = lerp1(c[4], c[6], dy), y4 = lerp1(c[5], c[7], dy);
-                const float z1 = lerp1(y1, y3, dx), z2 = lerp1(y2, y4, dx);
-                const float v = lerp1(z1, z2, dz);
+                const float v = field_value<U8>(raw[k], cs[k]);
                 m = (in[k] && v > m) ? v : m;
             }
         }
@@ -240,17 +167,13 @@ hipError_t launch_mip_march(const TestFrame& f, const MipFrame& g, const WorkTil
     const bool ess = (f.flags & 1) != 0 && bound != nullptr;
     const CropBox cb = crop ? *crop : CropBox{};   // (null: the box is off, the CROP = false instantiations)
     const size_t lds = (f.sep && f.sep_tab) ? (size_t)(f.S + 2 * kMipK) * sizeof(float4) : 0;
-#define VR_M4(ESS_, U8_, LAW_, CROP_)                                                                  \
-    hipLaunchKernelGGL((mip_march_kernel<ESS_, U8_, LAW_, CROP_>), dim3(n_blocks), dim3(kWgThreads), lds, st, f, \
-                       g, work, vol, bound, out, cb)
-#define VR_M3(ESS_, U8_, LAW_) do { if (crop) VR_M4(ESS_, U8_, LAW_, true); else VR_M4(ESS_, U8_, LAW_, false); } while (0)
-#define VR_M2(ESS_, U8_) do { if (f.sep == kLawPersp) VR_M3(ESS_, U8_, kLawPersp); else if (f.sep) VR_M3(ESS_, U8_, kLawSep); else VR_M3(ESS_, U8_, kLawGeneral); } while (0)
-#define VR_M1(ESS_) do { if (u8) VR_M2(ESS_, true); else VR_M2(ESS_, false); } while (0)
-    if (ess) VR_M1(true); else VR_M1(false);
-#undef VR_M1
-#undef VR_M2
-#undef VR_M3
-#undef VR_M4
+    with_flag(ess, [&](auto ESS) {
+        field_variant(u8, f.sep, crop != nullptr, [&](auto U8, auto LAW, auto CROP) {
+            hipLaunchKernelGGL((mip_march_kernel<decltype(ESS)::value, decltype(U8)::value, decltype(LAW)::value,
+                                                 decltype(CROP)::value>),
+                               dim3(n_blocks), dim3(kWgThreads), lds, st, f, g, work, vol, bound, out, cb);
+        });
+    });
     return hipGetLastError();
 }
 
